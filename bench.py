@@ -2,7 +2,8 @@
 """Benchmark: decoded codewords/s for the n=18432 / m=2048 BP decoder at 50
 iterations (BASELINE.json metric), one process per GPU.
 
-    python bench.py                       # N=1, 100k synthetic codewords per step
+    python bench.py                       # N=1, 100k synthetic codewords per step: the headline only
+    python bench.py --full                # + roofline, oracle check, CPU baseline, secondary legs
     python bench.py --gpus N              # N ranks: starts torch.distributed.run as a child
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
@@ -24,6 +25,14 @@ check, variable], final syndrome, hard-bit unpack, iteration counts).
 No data-path collective: ranks only meet in a barrier, a MAX of their elapsed
 times and a gather of their check counts (gloo, CPU tensors).  `value` = all
 codewords of all ranks / max elapsed.
+
+A plain run stops there: it sets up, warms up, times `--steps` decodes, writes
+its outputs if `--dump-outputs DIR` is given (DIR/iters.npy, valid.npy and the
+hard bits of a fixed, seeded sample of codewords, hard.npy / hard_rows.npy,
+as float32 / float64) and prints the line (metric, value, unit, ms_per_step,
+config).  Everything below -- the per-kernel HIP event timing and roofline,
+the oracle check, the CPU baseline, the secondary legs -- runs with `--full`
+only.
 
 Correctness of the timed decode, on every rank: the oracle decodes a sample of
 the rank's own shard -- its head (at N = 1 the cpu_baseline leg's sample, at
@@ -81,6 +90,14 @@ def parse():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="strong scaling: this many codewords split over the ranks by dist.shard (SURVEY 8(d) "
                          "config 4: --gpus 8 --global-batch 1000000 -> 125k per rank); 0 = weak scaling")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the benchmark measures or checks: per-kernel "
+                         "HIP event timing and the roofline, the oracle check of the timed decode, the CPU baseline "
+                         "and the secondary legs (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (float32 / "
+                         "float64): iters, valid and the hard bits of a fixed, seeded sample of codewords "
+                         "(hard_rows: their global indices); N > 1: every rank writes rank<r>_<name>.npy")
     ap.add_argument("--dump-dir", default="",
                     help="write each rank's outputs (shard start/size, iterations, valid flags, packed hard bits) "
                          "to <dir>/rank<r>.npz (tests)")
@@ -400,14 +417,15 @@ def roofline(eng, G, st, cw_iters, coded=False, cpw=None) -> dict:
     }
 
 
-def dna272(args, og, threads, max_iter=200):
+def dna272(args, og, threads, max_iter=200, reps=None, full=True, dump=""):
     """Config 2: the 272-codeword DNA-like batch (synth.dna_like_llrs, 72000
     reads) at the pipeline's max_iter, device-resident (the count differences
     k as int8 codes with the table k * ln49, LR = host libm exp as
     DNA_main.cpp:1344; --input fp64: fp64 LR), plus the end-to-end host-API
     time of the same decode (code table / host exp + PCIe + decode + copy
     back) -- the in-process replacement of decoder.py's 272 ldpc.exe runs
-    (decoder.py:553-562)."""
+    (decoder.py:553-562).  `reps` timed device decodes (default: at least
+    10); full=False stops after them: no host-API calls, no oracle."""
     import ldpc_amd as L
     import synth
     cw = synth.load_codewords()
@@ -437,7 +455,7 @@ def dna272(args, og, threads, max_iter=200):
     for _ in range(max(1, args.warmup)):
         step()
     eng.sync()
-    reps = max(args.steps, 10)
+    reps = reps or max(args.steps, 10)
     t = time.perf_counter()
     for _ in range(reps):
         step()
@@ -445,6 +463,15 @@ def dna272(args, og, threads, max_iter=200):
     el = (time.perf_counter() - t) / reps
     it = d_i.download(np.empty(B, np.int32))
     hard = d_h.download(np.empty((B, N), np.uint8))
+    out = {"workload": f"dna272-bp{max_iter}", "batch": B, "max_iter": max_iter, "input": args.input,
+           "value": round(B / el, 1), "unit": "codewords/s", "ms_per_decode_device": round(el * 1e3, 3),
+           "mean_iters": round(float(it.mean()), 3), "genie_ok": int((hard == cw).all(axis=1).sum())}
+    if dump:  # --dump-outputs: 272 x 18432 hard bits (20 MB as float32), iterations, valid flags
+        os.makedirs(dump, exist_ok=True)
+        for name, a in (("hard", hard), ("iters", it), ("valid", d_v.download(np.empty(B, np.uint8)))):
+            np.save(os.path.join(dump, f"{name}.npy"), a.astype(np.float32))
+    if not full:
+        return out
     # host API end to end (same decode, inputs in host memory): the DNA stage's
     # count differences k with the table k * ln49 (ldpc_decode_codes), and the
     # fp64 LLR matrix k * ln49 (ldpc_decode: lattice check + encode on the host)
@@ -477,9 +504,7 @@ def dna272(args, og, threads, max_iter=200):
     assert np.array_equal(h2, hard) and np.array_equal(it2, it)
     assert np.array_equal(h3, hard) and np.array_equal(it3, it) and np.array_equal(v3, v2)
     assert np.array_equal(h4, hard) and np.array_equal(it4, it) and np.array_equal(v4, v2)
-    out = {"workload": f"dna272-bp{max_iter}", "batch": B, "max_iter": max_iter, "input": args.input,
-           "value": round(B / el, 1), "unit": "codewords/s", "ms_per_decode_device": round(el * 1e3, 3),
-           "mean_iters": round(float(it.mean()), 3), "genie_ok": int((hard == cw).all(axis=1).sum()),
+    out.update({
            "host_api_ms_median": round(float(np.median(th)) * 1e3, 3),
            "host_api_ms_min": round(float(np.min(th)) * 1e3, 3),
            "host_api_calls": len(th),
@@ -498,7 +523,7 @@ def dna272(args, og, threads, max_iter=200):
            "pipeline_first_decode_ms_min": round(float(np.min(tf)) * 1e3, 3),
            "pipeline_first_decode_includes": "dna_pipeline.gpu_decode_fn(G).codes: the first decode of "
                                              "dna_pipeline.decode_trial when the LLR stage hands over its int8 codes "
-                                             "(dna_llr.LlrResult.codes) -- the host_api call above, from Python"}
+                                             "(dna_llr.LlrResult.codes) -- the host_api call above, from Python"})
     if og is not None:
         t = time.perf_counter()
         rh, _, rit, rv = og.decode_batch(llr, max_iter, threads=threads, want_post=False)
@@ -757,6 +782,25 @@ def config4_leg(args, L, dist, grp, G, dev, d_cw, cw, og, threads, total):
                               "every rank's shard: head, last rows (the lane pool's drain), random interior rows"}}
 
 
+DUMP_ROWS = 512  # codewords whose hard bits --dump-outputs keeps: 512 x 18432 float32 = 38 MB, all ranks together
+
+
+def dump_outputs(dirname, rank, world, b0, B, N, d_hard, iters, valid, seed):
+    """--dump-outputs: what the caller of the timed decode receives from its
+    last step -- iteration counts and valid flags of every codeword of the
+    shard and the hard bits of a fixed sample of its rows (chosen by `seed`
+    and the shard alone, so two builds dump the same codewords) -- as float32
+    .npy files; hard_rows holds the sample's global codeword indices."""
+    os.makedirs(dirname, exist_ok=True)
+    n = min(B, max(1, DUMP_ROWS // world))
+    rows = np.sort(np.random.default_rng([seed, b0, B]).choice(B, n, replace=False))
+    hard = np.stack([d_hard.download(np.empty(N, np.uint8), offset=int(r) * N) for r in rows])
+    pre = "" if world == 1 else f"rank{rank}_"
+    for name, a, dt in (("hard_rows", b0 + rows, np.float64), ("hard", hard, np.float32),
+                        ("iters", iters, np.float32), ("valid", valid, np.float32)):
+        np.save(os.path.join(dirname, f"{pre}{name}.npy"), np.asarray(a).astype(dt))
+
+
 def launch_ranks(n: int) -> int:
     """`bench.py --gpus N` run without a launcher: start N ranks under
     torch.distributed.run as a CHILD process (this process has not touched
@@ -786,10 +830,13 @@ def main():
     cpus = host_cpus()
     if args.workload == "dna272":
         og = _oracle().OracleGraph(os.path.join(ROOT, "tests", "golden", "decode_n18432_m2048_final.pchk")) \
-            if args.cpu_baseline else None
-        d = dna272(args, og, cpus["effective"], max_iter=args.max_iter if args.max_iter != 50 else 200)
+            if args.cpu_baseline and args.full else None
+        if args.steps < 1:
+            raise SystemExit("--steps must be at least 1")
+        d = dna272(args, og, cpus["effective"], max_iter=args.max_iter if args.max_iter != 50 else 200,
+                   reps=args.steps, full=args.full, dump=args.dump_outputs)
         out = {"metric": METRIC, "value": d.pop("value"), "unit": "codewords/s", "n_gpus": 1,
-               "steps": max(args.steps, 10), "warmup": args.warmup, "ms_per_step": d["ms_per_decode_device"],
+               "steps": args.steps, "warmup": args.warmup, "ms_per_step": d["ms_per_decode_device"],
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
                "data": "synthetic (DNA read simulator over the 272 true codewords)", "config": d}
         for k in ("check", "cpu_baseline"):
@@ -850,7 +897,7 @@ def main():
     passes = -(-B // eng.cap)
     groups = -(-(-(-B // passes) // 64) // eng.group_tiles)
     est = args.steps * passes * groups * args.max_iter
-    eng.profile(0 if args.no_profile else max(1, -(-est // 1000)))
+    eng.profile(0 if args.no_profile or not args.full else max(1, -(-est // 1000)))
     grp.barrier()
     eng.sync()
     t0 = time.perf_counter()
@@ -870,6 +917,8 @@ def main():
         hard = d_hard.download(np.empty((B, N), np.uint8))
         np.savez(os.path.join(args.dump_dir, f"rank{rank}.npz"), b0=b0, B=B, world=world, iters=iters, valid=valid,
                  hard=np.packbits(hard, axis=1))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, b0, B, N, d_hard, iters, valid, args.seed)
 
     cw_iters = float(iters.sum()) * args.steps  # executed codeword-iterations (this rank)
     out = {
@@ -888,8 +937,17 @@ def main():
                    "continuous": eng.continuous, "resident_pool": eng.resident,
                    "compressed_msa": eng.msa_compressed, "syndrome_split": eng.syndrome_split,
                    "mean_iters": round(float(iters.mean()), 3), "valid_frac": round(float(valid.mean()), 4)},
-        "roofline": roofline(eng, G, st, cw_iters, args.input == "code", args.var_cpw or None),
     }
+    if not args.full:
+        # the plain run ends with its headline: no event timing, oracle, CPU baseline or secondary leg
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        for b in (d_in, d_hard, d_iters, d_valid, d_cw):
+            b.free()
+        eng.close()
+        grp.close()
+        return
+    out["roofline"] = roofline(eng, G, st, cw_iters, args.input == "code", args.var_cpw or None)
 
     # ---- correctness of the timed decode: every rank checks its own shard ----
     og = _oracle().OracleGraph(os.path.join(ROOT, "tests", "golden", "decode_n18432_m2048_final.pchk"))

@@ -28,7 +28,7 @@ def _bench(*args):
 @pytest.mark.parametrize("algo,p", [("bp", 0.02), ("msa", 0.002)])
 def test_bench_bsc_line(gpu, algo, p):
     out = _bench("--algo", algo, "--p", str(p), "--batch-per-gpu", "2048", "--steps", "1", "--warmup", "1",
-                 "--cpu-seconds", "1", "--secondary", "0")
+                 "--cpu-seconds", "1", "--secondary", "0", "--full")
     assert out["steps"] == 1 and out["dtype"] == "f64"
     rl = out["roofline"]
     # BP's default schedule is the resident pool, sized to the Infinity Cache (MALL)
@@ -48,7 +48,7 @@ def test_bench_secondary_legs(gpu):
     """The driver-run line's secondary legs (config 5 min-sum, config 2 DNA
     batch through the host API), shrunk: each has its own oracle check."""
     out = _bench("--batch-per-gpu", "1024", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0.5",
-                 "--msa-batch", "8192", "--hbm-batch", "2048")
+                 "--msa-batch", "8192", "--hbm-batch", "2048", "--full")
     sec = out["secondary"]
     m = sec["config5_msa_1m"]
     assert m["batch"] == 8192 and m["compressed_msa"] and m["check"]["mismatches"] == 0 and m["check"]["checked"] >= 8
@@ -72,6 +72,32 @@ def test_bench_secondary_legs(gpu):
     assert out["roofline"]["frac_hbm_streaming"] == h["roofline"]["frac"]
     # the pipeline's first decode from the LLR stage's int8 codes
     assert d["pipeline_first_decode_ms_median"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(gpu, tmp_path):
+    """A plain run (no --full) prints the headline only -- no roofline, oracle
+    check, CPU baseline or secondary leg -- times exactly --steps decodes, and
+    --dump-outputs writes what the last step computed as float32 / float64
+    .npy files: iterations and valid flags of every codeword, the hard bits
+    of a sample of rows, equal to the same run's --dump-dir record."""
+    import numpy as np
+    d, z = str(tmp_path / "out"), str(tmp_path / "npz")
+    out = _bench("--batch-per-gpu", "1100", "--max-iter", "20", "--p", "0.0065", "--steps", "2", "--warmup", "1",
+                 "--dump-outputs", d, "--dump-dir", z)
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["dtype"] == "f64" and out["ms_per_step"] > 0
+    assert abs(out["value"] * out["ms_per_step"] / 1e3 / 1100 - 1) < 1e-3  # value = codewords / step time
+    for k in ("roofline", "check", "cpu_baseline", "secondary"):
+        assert k not in out
+    ref = np.load(os.path.join(z, "rank0.npz"))
+    got = {n: np.load(os.path.join(d, n + ".npy")) for n in ("hard", "hard_rows", "iters", "valid")}
+    assert sorted(os.listdir(d)) == ["hard.npy", "hard_rows.npy", "iters.npy", "valid.npy"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+    rows = got["hard_rows"].astype(np.int64)
+    assert rows.shape == (512,) and np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 1100
+    assert np.array_equal(got["iters"], ref["iters"]) and np.array_equal(got["valid"], ref["valid"])
+    assert len(np.unique(got["iters"])) > 2 and got["valid"].any()  # a decode that converges at varied iterations
+    assert np.array_equal(got["hard"], np.unpackbits(ref["hard"], axis=1)[rows])
 
 
 def test_bench_dna272_line(gpu):

@@ -44,7 +44,7 @@ def _load(d, world, N):
 
 
 SHARD_ARGS = ["--global-batch", "1000", "--max-iter", "20", "--p", "0.0065", "--steps", "1", "--warmup", "0",
-              "--no-profile", "--cpu-baseline", "0"]
+              "--no-profile", "--cpu-baseline", "0", "--full"]
 LAUNCH_ENV = ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK", "MASTER_PORT",
               "TORCHELASTIC_RUN_ID")
 
@@ -121,8 +121,8 @@ def test_plain_bench_gpus2_cpu_baseline_and_config4_leg(gpu):
     batch -- with both ranks' oracle checks of their dist.shard ranges."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch-per-gpu", "256",
                         "--max-iter", "20", "--p", "0.0065", "--steps", "1", "--warmup", "0", "--no-profile",
-                        "--cpu-seconds", "1", "--config4", "1000"], cwd=ROOT, env=_env(), capture_output=True,
-                       text=True, timeout=280)
+                        "--cpu-seconds", "1", "--config4", "1000", "--full"], cwd=ROOT, env=_env(),
+                       capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _line(r.stdout)
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["check"]["mismatches"] == 0
@@ -142,7 +142,8 @@ def test_bench_global_batch_odd_split(gpu, tmp_path):
     """A global batch that does not divide: dist.shard sizes differ by one;
     single process -> the whole range."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--global-batch", "129", "--max-iter", "5",
-                        "--steps", "1", "--warmup", "0", "--cpu-seconds", "0.5", "--dump-dir", str(tmp_path)],
+                        "--steps", "1", "--warmup", "0", "--cpu-seconds", "0.5", "--dump-dir", str(tmp_path),
+                        "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
     out = _line(r.stdout)

@@ -12,7 +12,7 @@ cp $lib $out/keep.so
 for r in $(seq 1 ${ROUNDS:-3}); do
   for v in ${VARIANTS:-old new}; do
     cp ab_lib/libldpc_amd_$v.so $lib
-    timeout -k 10 200 python bench.py --cpu-baseline 0 "$@" > $out/$v$r.json 2> $out/$v$r.err; brc=$?
+    timeout -k 10 200 python bench.py --full --cpu-baseline 0 "$@" > $out/$v$r.json 2> $out/$v$r.err; brc=$?
     if [ $brc -ne 0 ] && { [ -z "${ABIGNORE:-}" ] || [ ! -s $out/$v$r.json ]; }; then cp $out/keep.so $lib; exit 1; fi
     python -c "import json;d=json.load(open('$out/$v$r.json'));r=d['roofline'];print('$v', d['value'], r['frac'], r['avg_ms']['check'], r['avg_ms']['variable'], r['avg_ms']['syndrome'])"
   done

@@ -9,6 +9,6 @@ run() { local name=$1 lim=$2; shift 2; timeout -k 10 "$lim" "$@" > "$OUT/$name.l
 run pytest_all 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread --durations=30
 run smoke 120 python -c "import __graft_entry__ as g; g.smoke()"
 run bench_driver 400 python -u bench.py --steps 20 --warmup 5
-run trace_default 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace_default" -o run --output-format csv -- python3 "$R/bench.py"
+run trace_default 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace_default" -o run --output-format csv -- python3 "$R/bench.py" --full
 rm -f "$OUT"/trace_default/*kernel_trace.csv
 exit 0

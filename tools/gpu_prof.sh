@@ -13,7 +13,7 @@ run() { local name=$1 lim=$2; shift 2; timeout -k 10 "$lim" "$@" > "$OUT/$name.o
 if [ -n "$K" ]; then
   run pytest 400 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread -k "$K" --durations=10
 fi
-if [ -z "${NOBENCH:-}" ]; then run bench_default 400 python bench.py; fi
+if [ -z "${NOBENCH:-}" ]; then run bench_default 400 python bench.py --full; fi
 if [ -n "${AB:-}" ]; then
   run ab 400 python -u tools/ab_engines.py $AB
 fi

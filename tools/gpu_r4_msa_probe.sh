@@ -4,7 +4,7 @@
 # group, lane pool.  Two alternating rounds, one bench line per setting.
 set -o pipefail
 out=gpurun_out/${1:-msaprobe}; mkdir -p $out
-B="--algo msa --p 0.002 --batch-per-gpu 1000000 --secondary 0 --steps 2 --warmup 1 --cpu-baseline 0"
+B="--full --algo msa --p 0.002 --batch-per-gpu 1000000 --secondary 0 --steps 2 --warmup 1 --cpu-baseline 0"
 i=0
 for r in 1 2; do
   for v in "" "--var-cpw 4" "--var-cpw 1" "--group-tiles 8" "--chunk 2048" "--chunk 2048 --group-tiles 8"; do

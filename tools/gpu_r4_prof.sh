@@ -10,7 +10,7 @@ TAG=${1:-r4prof}
 WHICH=${2:-both}
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out/$TAG; mkdir -p "$OUT"; cd "$R"; export TMPDIR=/tmp
 if [ "${REHEARSAL:-1}" != 0 ]; then
-timeout -k 10 300 python bench.py --gpus 8 --batch-per-gpu 2048 --steps 2 --warmup 1 --max-iter 50 \
+timeout -k 10 300 python bench.py --full --gpus 8 --batch-per-gpu 2048 --steps 2 --warmup 1 --max-iter 50 \
   > "$OUT/gpus8_rehearsal.json" 2> "$OUT/gpus8_rehearsal.err" || { echo "rehearsal rc=$?"; tail -20 "$OUT/gpus8_rehearsal.err"; exit 1; }
 echo "rehearsal ok"; tail -c 400 "$OUT/gpus8_rehearsal.json"; echo
 fi

@@ -13,7 +13,7 @@
 set -u
 TAG=${1:-r5prof}
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out/$TAG; mkdir -p "$OUT"; cd "$R"; export TMPDIR=/tmp
-timeout -k 10 400 python bench.py --gpus 8 --batch-per-gpu 2048 --steps 2 --warmup 1 --config4 16384 --cpu-seconds 4 \
+timeout -k 10 400 python bench.py --full --gpus 8 --batch-per-gpu 2048 --steps 2 --warmup 1 --config4 16384 --cpu-seconds 4 \
   > "$OUT/gpus8_rehearsal.json" 2> "$OUT/gpus8_rehearsal.err" || { echo "rehearsal rc=$?"; tail -20 "$OUT/gpus8_rehearsal.err"; exit 1; }
 echo "rehearsal ok"; tail -c 300 "$OUT/gpus8_rehearsal.json"; echo
 pmc() {  # pmc <name> <bench args...>
