@@ -26,6 +26,7 @@
 
 #include "../../include/ldpc_amd.h"
 #include "engine.hpp"
+#include "gf2.hpp"
 #include "graph.hpp"
 #include "host_simd.hpp"
 
@@ -313,6 +314,109 @@ struct ldpc_graph {
 
 struct ldpc_engine {
     std::unique_ptr<Engine> e;
+};
+
+namespace {
+
+// Workspace of one encode call in flight (ballot words + row parities of a
+// pass).  `ev` is recorded after the call's last kernel, and the next call to
+// take the workspace makes its stream wait for it: calls on different streams
+// may share workspaces without a host wait.
+struct EncWork {
+    uint64_t* buf = nullptr;
+    int64_t tiles = 0;
+    hipEvent_t ev = nullptr;
+    bool recorded = false;
+};
+
+// An encoder's state on one device: T, the position lists and the CSR arrays
+// (uploaded once), the library's own stream, idle workspaces.
+struct EncCtx {
+    int device = 0;
+    ldpc::EncoderDev d;
+    hipStream_t own = nullptr;
+    std::vector<EncWork> idle;
+
+    ~EncCtx()
+    {
+        hipSetDevice(device);
+        if (own) hipStreamSynchronize(own);
+        for (auto& wk : idle) {
+            if (wk.ev) { hipEventSynchronize(wk.ev); hipEventDestroy(wk.ev); }
+            hipFree(wk.buf);
+        }
+        hipFree(d.info_pos); hipFree(d.par_pos); hipFree(d.row_ptr); hipFree(d.col_idx); hipFree(d.T);
+        if (own) hipStreamDestroy(own);
+    }
+};
+
+template <typename T>
+int enc_upload(T** dst, const std::vector<T>& v)
+{
+    LDPC_HIP(hipMalloc((void**)dst, std::max<size_t>(v.size(), 1) * sizeof(T)));
+    if (!v.empty()) LDPC_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return LDPC_OK;
+}
+
+constexpr int64_t kEncXfer = 16384;  // ldpc_encode: codewords per pass through device memory
+
+}  // namespace
+
+struct ldpc_encoder {
+    ldpc::HostEncoder h;
+    std::mutex mu;  // ctx and every EncCtx::idle
+    std::vector<std::unique_ptr<EncCtx>> ctx;
+
+    // the device context, created (and the encoder uploaded) on first use
+    int context(int device, EncCtx** out)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto& c : ctx)
+            if (c->device == device) { *out = c.get(); return LDPC_OK; }
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_error("no HIP device"); return LDPC_ERR_DEVICE; }
+        if (device < 0 || device >= ndev) { set_error("device ordinal out of range"); return LDPC_ERR_DEVICE; }
+        LDPC_HIP(hipSetDevice(device));
+        auto c = std::make_unique<EncCtx>();
+        c->device = device;
+        c->d.M = h.M; c->d.N = h.N; c->d.K = h.K; c->d.rank = h.rank; c->d.Mw = h.Mw;
+        int rc;
+        if ((rc = enc_upload(&c->d.info_pos, h.info_pos)) || (rc = enc_upload(&c->d.par_pos, h.par_pos)) ||
+            (rc = enc_upload(&c->d.row_ptr, h.row_ptr)) || (rc = enc_upload(&c->d.col_idx, h.col_idx)) ||
+            (rc = enc_upload(&c->d.T, h.T)))
+            return rc;
+        LDPC_HIP(hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking));
+        *out = c.get();
+        ctx.push_back(std::move(c));
+        return LDPC_OK;
+    }
+    int take(EncCtx& c, int64_t tiles, EncWork* out)
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            for (size_t i = 0; i < c.idle.size(); i++)
+                if (c.idle[i].tiles >= tiles) {
+                    *out = c.idle[i];
+                    c.idle.erase(c.idle.begin() + (long)i);
+                    return LDPC_OK;
+                }
+        }
+        EncWork wk;
+        wk.tiles = tiles;
+        LDPC_HIP(hipMalloc((void**)&wk.buf, ldpc::encode_workspace_words(c.d, tiles) * sizeof(uint64_t)));
+        if (hipEventCreateWithFlags(&wk.ev, hipEventDisableTiming) != hipSuccess) {
+            hipFree(wk.buf);
+            set_error("hipEventCreateWithFlags failed");
+            return LDPC_ERR_DEVICE;
+        }
+        *out = wk;
+        return LDPC_OK;
+    }
+    void give(EncCtx& c, const EncWork& wk)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        c.idle.push_back(wk);
+    }
 };
 
 static int fail(int rc, int* err)
@@ -864,6 +968,115 @@ int ldpc_engine_stats(ldpc_engine* e, ldpc_kernel_stats* out)
         out->ms[c] = e->e->ms[c];
     }
     return LDPC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// systematic encoding (gf2.hpp: definition, construction, host encoder;
+// encode_kernels.hpp: the device path)
+// ---------------------------------------------------------------------------
+ldpc_encoder* ldpc_encoder_create(const ldpc_graph* g, int* err)
+{
+    if (!g) { set_error("null graph"); fail(LDPC_ERR_ARG, err); return nullptr; }
+    auto e = std::make_unique<ldpc_encoder>();
+    std::string msg;
+    int rc = ldpc::build_encoder(g->h, e->h, &msg);
+    if (rc) { set_error(msg); fail(rc, err); return nullptr; }
+    if (err) *err = LDPC_OK;
+    return e.release();
+}
+
+void ldpc_encoder_free(ldpc_encoder* e) { delete e; }
+
+int ldpc_encoder_info(const ldpc_encoder* e, int32_t* N, int32_t* K, int32_t* rank, int32_t* info_pos, int32_t* par_pos)
+{
+    if (!e) { set_error("null encoder"); return LDPC_ERR_ARG; }
+    if (N) *N = e->h.N;
+    if (K) *K = e->h.K;
+    if (rank) *rank = e->h.rank;
+    if (info_pos) std::copy(e->h.info_pos.begin(), e->h.info_pos.end(), info_pos);
+    if (par_pos) std::copy(e->h.par_pos.begin(), e->h.par_pos.end(), par_pos);
+    return LDPC_OK;
+}
+
+static int encode_args(const ldpc_encoder* e, const void* msg, int64_t B, const void* cw)
+{
+    if (!e) { set_error("null encoder"); return LDPC_ERR_ARG; }
+    if (B < 0) { set_error("B must be >= 0"); return LDPC_ERR_ARG; }
+    if (B > 0 && (!msg || !cw)) { set_error("the messages and the codeword buffer are required"); return LDPC_ERR_ARG; }
+    if (B > (int64_t)(PTRDIFF_MAX / 8) / (int64_t)std::max<int32_t>(1, e->h.N)) {
+        set_error("batch too large: B * N bytes overflow the address space");
+        return LDPC_ERR_ARG;
+    }
+    return LDPC_OK;
+}
+
+int ldpc_encode_host(const ldpc_encoder* e, const uint8_t* msg, int64_t B, uint8_t* cw_out)
+{
+    int rc = encode_args(e, msg, B, cw_out);
+    if (rc || B == 0) return rc;
+    std::string err;
+    rc = ldpc::encode_host(e->h, msg, B, cw_out, &err);
+    if (rc) set_error(err);
+    return rc;
+}
+
+int ldpc_encoder_encode_device(const ldpc_encoder* ec, int32_t device, void* stream, const uint8_t* d_msg, int64_t B,
+                               uint8_t* d_cw)
+{
+    int rc = encode_args(ec, d_msg, B, d_cw);
+    if (rc || B == 0) return rc;
+    ldpc_encoder* e = const_cast<ldpc_encoder*>(ec);  // the device contexts are a cache behind e->mu
+    EncCtx* c = nullptr;
+    if ((rc = e->context(device, &c))) return rc;
+    LDPC_HIP(hipSetDevice(device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->own;
+    EncWork wk;
+    if ((rc = e->take(*c, std::min<int64_t>(ldpc::kEncPassTiles, (B + 63) / 64), &wk))) return rc;
+    hipError_t he = wk.recorded ? hipStreamWaitEvent(st, wk.ev, 0) : hipSuccess;
+    if (he == hipSuccess) {
+        rc = ldpc::encode_launch(c->d, st, d_msg, B, d_cw, wk.buf, wk.tiles);
+        he = hipEventRecord(wk.ev, st);
+        wk.recorded = he == hipSuccess;
+    }
+    e->give(*c, wk);
+    if (he != hipSuccess) { set_error(std::string("encode: ") + hipGetErrorString(he)); return LDPC_ERR_DEVICE; }
+    if (rc) return rc;
+    // no stream of the caller's to wait on: the call itself waits
+    if (!stream) LDPC_HIP(hipStreamSynchronize(c->own));
+    return LDPC_OK;
+}
+
+int ldpc_encode(const ldpc_encoder* e, const uint8_t* msg, int64_t B, uint8_t* cw_out, int32_t device)
+{
+    int rc = encode_args(e, msg, B, cw_out);
+    if (rc || B == 0) return rc;
+    const size_t K = (size_t)e->h.K, N = (size_t)e->h.N;
+    size_t bad = 0;
+    if (!ldpc::message_bytes_ok(msg, (size_t)B * K, &bad)) {
+        set_error("message byte " + std::to_string(bad % K) + " of message " + std::to_string(bad / K) +
+                  " is neither 0 nor 1");
+        return LDPC_ERR_ARG;
+    }
+    if (ldpc_device_count() < 1) { set_error("no HIP device (ldpc_encode_host encodes on the CPU)"); return LDPC_ERR_DEVICE; }
+    if (device < 0 || device >= ldpc_device_count()) { set_error("device ordinal out of range"); return LDPC_ERR_DEVICE; }
+    LDPC_HIP(hipSetDevice(device));
+    // any B: passes of kEncXfer codewords through device memory
+    const size_t X = (size_t)std::min<int64_t>(B, kEncXfer);
+    uint8_t* d_msg = nullptr;
+    uint8_t* d_cw = nullptr;
+    hipError_t he = hipMalloc((void**)&d_msg, X * K);
+    if (he == hipSuccess) he = hipMalloc((void**)&d_cw, X * N);
+    for (int64_t b0 = 0; he == hipSuccess && rc == LDPC_OK && b0 < B; b0 += (int64_t)X) {
+        const size_t Bc = (size_t)std::min<int64_t>((int64_t)X, B - b0);
+        he = hipMemcpy(d_msg, msg + (size_t)b0 * K, Bc * K, hipMemcpyHostToDevice);
+        if (he != hipSuccess) break;
+        rc = ldpc_encoder_encode_device(e, device, nullptr, d_msg, (int64_t)Bc, d_cw);  // waits
+        if (rc == LDPC_OK) he = hipMemcpy(cw_out + (size_t)b0 * N, d_cw, Bc * N, hipMemcpyDeviceToHost);
+    }
+    hipFree(d_msg);
+    hipFree(d_cw);
+    if (he != hipSuccess) { set_error(std::string("ldpc_encode: ") + hipGetErrorString(he)); return LDPC_ERR_DEVICE; }
+    return rc;
 }
 
 void* ldpc_host_alloc(size_t bytes)

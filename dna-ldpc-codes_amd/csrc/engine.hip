@@ -36,6 +36,7 @@
 #include "engine.hpp"
 #include "kernels.hpp"
 #include "kernels_int.hpp"
+#include "encode_kernels.hpp"
 
 namespace ldpc {
 
@@ -1247,6 +1248,49 @@ int Engine::pack_bits(const uint8_t* d_in, uint8_t* d_out, int64_t nbytes)
     const int64_t blocks = std::min<int64_t>(4096, (nbytes + 255) / 256);
     klaunch(dev::k_pack_bits, dim3((unsigned)blocks), dim3(256), 0, stream, (const uint64_t*)d_in, d_out, nbytes);
     LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+// Batched systematic encode (encode_kernels.hpp): per pass of <= ws_tiles
+// tiles, clear the ballot words, pack the messages into the information
+// positions, row parities (sparse step), T x s into the parity positions
+// (dense step), unpack to one byte per bit.
+int encode_launch(const EncoderDev& d, hipStream_t stream, const uint8_t* d_msg, int64_t B, uint8_t* d_cw, uint64_t* ws,
+                  int64_t ws_tiles)
+{
+    using namespace dev;
+    if (B <= 0) return LDPC_OK;
+    if (!d_msg || !d_cw || !ws || ws_tiles < 1 || ws_tiles > kEncPassTiles) { set_error("encode: bad arguments"); return LDPC_ERR_ARG; }
+    const size_t N = (size_t)d.N, K = (size_t)d.K;
+    uint64_t* w = ws;
+    uint64_t* s = ws + (size_t)ws_tiles * N;
+    const size_t s_bytes = (size_t)d.Mw * TILE * sizeof(uint64_t);
+    const bool in_lds = s_bytes <= ENC_DENSE_LDS_BYTES;
+    for (int64_t b0 = 0; b0 < B; b0 += ws_tiles * TILE) {
+        const int64_t Bc = std::min<int64_t>(ws_tiles * TILE, B - b0);
+        const unsigned tiles = (unsigned)((Bc + TILE - 1) / TILE);
+        const uint8_t* m = d_msg + (size_t)b0 * K;
+        const int vec4 = ((reinterpret_cast<uintptr_t>(m) | K) & 3) == 0;
+        LDPC_HIP(hipMemsetAsync(w, 0, (size_t)tiles * N * sizeof(uint64_t), stream));
+        hipLaunchKernelGGL(k_enc_pack, dim3((unsigned)((K + ENC_PACK_COLS - 1) / ENC_PACK_COLS), tiles), dim3(256), 0, stream,
+                           m, d.info_pos, w, Bc, d.K, d.N, vec4);
+        if (d.M > 0)
+            hipLaunchKernelGGL(k_enc_rows, dim3((unsigned)((d.M + 3) / 4), tiles), dim3(256), 0, stream, w, d.row_ptr,
+                               d.col_idx, s, d.M, d.N);
+        if (d.rank > 0) {
+            const dim3 grid((unsigned)((d.rank + ENC_DENSE_ROWS - 1) / ENC_DENSE_ROWS), tiles);
+            if (in_lds)
+                hipLaunchKernelGGL(k_enc_dense<true>, grid, dim3(256), (uint32_t)s_bytes, stream, d.T, s, d.par_pos, w,
+                                   d.rank, d.M, d.Mw, d.N);
+            else
+                hipLaunchKernelGGL(k_enc_dense<false>, grid, dim3(256), 0, stream, d.T, s, d.par_pos, w, d.rank, d.M,
+                                   d.Mw, d.N);
+        }
+        const int64_t nblk = Bc * (((int64_t)N + 255) / 256);
+        hipLaunchKernelGGL(k_unpack_hard, dim3((unsigned)std::min<int64_t>(nblk, 1 << 20)), dim3(256), 0, stream, w,
+                           d_cw + (size_t)b0 * N, Bc, d.N);
+        LDPC_HIP(hipGetLastError());
+    }
     return LDPC_OK;
 }
 

@@ -182,4 +182,26 @@ struct Engine {
 // bytes of device memory per resident codeword
 int64_t engine_bytes_per_codeword(const HostGraph& g);
 
+// Device copy of an encoder (gf2.hpp HostEncoder), uploaded once per
+// (encoder, device) by capi.cpp.
+struct EncoderDev {
+    int32_t M = 0, N = 0, K = 0, rank = 0, Mw = 0;
+    int32_t* info_pos = nullptr;  // [K]
+    int32_t* par_pos = nullptr;   // [rank]
+    int32_t* row_ptr = nullptr;   // [M+1]
+    int32_t* col_idx = nullptr;   // [E]
+    uint64_t* T = nullptr;        // [rank][Mw]
+};
+
+// Encode passes hold at most this many 64-codeword tiles (16 384 codewords;
+// the DNA code's ballot words of a pass: 38 MB, L2 / Infinity Cache resident).
+constexpr int64_t kEncPassTiles = 256;
+// 64-bit words of workspace for passes of `tiles` tiles: w [tiles][N] + s [tiles][M]
+inline size_t encode_workspace_words(const EncoderDev& d, int64_t tiles) { return (size_t)tiles * ((size_t)d.N + (size_t)d.M); }
+// Enqueue the encode of d_msg [B][K] u8 (bit 0 of each byte) into d_cw
+// [B][N] u8 on `stream`, in passes of ws_tiles <= kEncPassTiles tiles through
+// the workspace ws (encode_workspace_words(d, ws_tiles)).  Asynchronous.
+int encode_launch(const EncoderDev& d, hipStream_t stream, const uint8_t* d_msg, int64_t B, uint8_t* d_cw, uint64_t* ws,
+                  int64_t ws_tiles);
+
 }  // namespace ldpc

@@ -136,6 +136,8 @@ EXPORTS = [
     "ldpc_engine_create", "ldpc_engine_create_ex", "ldpc_engine_info", "ldpc_engine_free", "ldpc_engine_decode", "ldpc_engine_sync", "ldpc_engine_stream",
     "ldpc_engine_decode_codes", "ldpc_engine_gen_bsc", "ldpc_engine_gen_bsc_codes", "ldpc_engine_set_params", "ldpc_engine_profile", "ldpc_engine_stats", "ldpc_dev_malloc", "ldpc_dev_free",
     "ldpc_dev_memcpy", "ldpc_host_alloc", "ldpc_host_free", "ldpc_dna_llr", "ldpc_dna_llr_codes", "ldpc_dna_edit_distance", "ldpc_write_soft_files", "ldpc_py_float_repr",
+    "ldpc_encoder_create", "ldpc_encoder_free", "ldpc_encoder_info", "ldpc_encode_host", "ldpc_encode",
+    "ldpc_encoder_encode_device",
 ]
 
 
@@ -202,6 +204,14 @@ def lib():
         L.ldpc_dev_malloc.restype = vp
         L.ldpc_dev_free.argtypes = [i32, vp]
         L.ldpc_dev_memcpy.argtypes = [i32, vp, vp, C.c_size_t, i32]
+        L.ldpc_encoder_create.argtypes = [vp, pint]
+        L.ldpc_encoder_create.restype = vp
+        L.ldpc_encoder_free.argtypes = [vp]
+        L.ldpc_encoder_free.restype = None
+        L.ldpc_encoder_info.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.ldpc_encode_host.argtypes = [vp, vp, i64, vp]
+        L.ldpc_encode.argtypes = [vp, vp, i64, vp, i32]
+        L.ldpc_encoder_encode_device.argtypes = [vp, i32, vp, vp, i64, vp]
         _lib = L
         return L
 
@@ -300,6 +310,14 @@ class Graph:
     def save_alist(self, path: str):
         """Write an alist file in RS_LDPC.c's layout (RS_LDPC.c:434-474)."""
         _check(lib().ldpc_graph_save_alist(self._h, os.fsencode(path)))
+
+    def encoder(self) -> "Encoder":
+        """The graph's systematic encoder (built once, cached; it stays
+        usable after the graph is closed)."""
+        e = getattr(self, "_enc", None)
+        if e is None or e._h is None:
+            e = self._enc = Encoder(self)
+        return e
 
     def close(self):
         if getattr(self, "_h", None):
@@ -622,6 +640,11 @@ class Engine:
     def sync(self):
         _check(lib().ldpc_engine_sync(self._h))
 
+    @property
+    def stream(self):
+        """The engine's HIP stream (hipStream_t as a ctypes void pointer)."""
+        return C.c_void_p(lib().ldpc_engine_stream(self._h))
+
     def profile(self, stride: int):
         """HIP-event timing of every `stride`-th launch per kernel class (0: off)."""
         _check(lib().ldpc_engine_profile(self._h, int(stride)))
@@ -635,6 +658,92 @@ class Engine:
     def close(self):
         if getattr(self, "_h", None):
             lib().ldpc_engine_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------------------
+# systematic encoder (ldpc_encoder_*): the write half of the codec
+# ---------------------------------------------------------------------------
+class Encoder:
+    """Systematic encoder of a graph (include/ldpc_amd.h, "Systematic
+    encoding"): message bit k sits at codeword position info_pos[k], the
+    rank parity positions par_pos are solved from H c = 0.
+
+        enc = G.encoder()
+        cw = enc.encode(msg)            # [B][K] -> [B][N] on the GPU
+        assert (enc.extract(cw) == msg).all()
+
+    Built on the host from the graph alone; it keeps no reference to it."""
+
+    def __init__(self, g: Graph):
+        err = C.c_int(0)
+        self._h = lib().ldpc_encoder_create(g.handle, C.byref(err))
+        if not self._h:
+            raise LdpcError(err.value, (lib().ldpc_last_error() or b"").decode(errors="replace"))
+        N, K, r = C.c_int32(), C.c_int32(), C.c_int32()
+        _check(lib().ldpc_encoder_info(self._h, C.byref(N), C.byref(K), C.byref(r), None, None))
+        self.N, self.K, self.rank = N.value, K.value, r.value
+        self.info_pos = np.zeros(self.K, np.int32)
+        self.par_pos = np.zeros(self.rank, np.int32)
+        _check(lib().ldpc_encoder_info(self._h, None, None, None, _ptr(self.info_pos),
+                                       _ptr(self.par_pos) if self.rank else None))
+
+    def _messages(self, msg):
+        m = np.asarray(msg)
+        if m.dtype != np.bool_ and not np.issubdtype(m.dtype, np.integer):
+            raise ValueError(f"messages must be an integer or bool array (got {m.dtype})")
+        single = m.ndim == 1
+        if single:
+            m = m[None, :]
+        if m.ndim != 2 or m.shape[1] != self.K:
+            raise ValueError(f"messages must have shape [B][{self.K}]")
+        if m.dtype != np.bool_ and m.size and (int(m.min()) < 0 or int(m.max()) > 1):
+            raise ValueError("message values outside {0, 1}")
+        return np.ascontiguousarray(m, dtype=np.uint8), single
+
+    def encode_host(self, msg) -> np.ndarray:
+        """Codewords u8 [B][N] (or [N] for a 1-D message) on the CPU."""
+        m, single = self._messages(msg)
+        cw = np.empty((m.shape[0], self.N), np.uint8)
+        _check(lib().ldpc_encode_host(self._h, _ptr(m), m.shape[0], _ptr(cw)))
+        return cw[0] if single else cw
+
+    def encode(self, msg, device: int = 0) -> np.ndarray:
+        """Codewords u8 [B][N] (or [N] for a 1-D message) on GPU `device`."""
+        m, single = self._messages(msg)
+        cw = np.empty((m.shape[0], self.N), np.uint8)
+        _check(lib().ldpc_encode(self._h, _ptr(m), m.shape[0], _ptr(cw), int(device)))
+        return cw[0] if single else cw
+
+    def encode_device(self, d_msg, B: int, d_cw, device: int = 0, stream=None):
+        """d_msg [B][K] u8 -> d_cw [B][N] u8 on the device (DeviceBuffers or
+        device pointers).  stream: a hipStream_t (Engine.stream) -- the call
+        only enqueues -- or None: the library's own stream, and the call
+        returns when the codewords are written."""
+        pm = C.c_void_p(d_msg.ptr) if isinstance(d_msg, DeviceBuffer) else d_msg
+        pc = C.c_void_p(d_cw.ptr) if isinstance(d_cw, DeviceBuffer) else d_cw
+        if isinstance(d_msg, DeviceBuffer) and B * self.K > d_msg.nbytes:
+            raise ValueError("d_msg is smaller than B x K bytes")
+        if isinstance(d_cw, DeviceBuffer) and B * self.N > d_cw.nbytes:
+            raise ValueError("d_cw is smaller than B x N bytes")
+        _check(lib().ldpc_encoder_encode_device(self._h, int(device), stream, pm, int(B), pc))
+
+    def extract(self, cw) -> np.ndarray:
+        """The message bits of codewords: cw[..., info_pos]."""
+        c = np.asarray(cw)
+        if c.shape[-1:] != (self.N,):
+            raise ValueError(f"codewords must have shape [...][{self.N}]")
+        return c[..., self.info_pos]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().ldpc_encoder_free(self._h)
             self._h = None
 
     def __del__(self):

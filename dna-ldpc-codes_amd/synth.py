@@ -108,6 +108,26 @@ def bsc_llrs(codewords: np.ndarray, b0: int, B: int, seed: int, p: float, mag: f
     return np.where(y == 1, -mag, mag)
 
 
+# --- random messages and fresh codewords (any code with an encoder) ---------
+def random_messages(K: int, b0: int, B: int, seed: int) -> np.ndarray:
+    """[B][K] uint8: bit k of message b (b0 <= b < b0 + B) is the low bit of
+    splitmix64(((b << 24) | k) ^ splitmix64(seed)) -- the BSC generator's
+    keying, so a range gives the same messages however it is split."""
+    if not 0 <= K < (1 << 24):
+        raise ValueError("K must be below 2^24 (the key holds k in 24 bits)")
+    seedmix = _splitmix64(np.array([seed], np.uint64))[0]
+    b = np.arange(b0, b0 + B, dtype=np.uint64)[:, None]
+    k = np.arange(K, dtype=np.uint64)[None, :]
+    return np.ascontiguousarray((_splitmix64(((b << np.uint64(24)) | k) ^ seedmix) & np.uint64(1)).astype(np.uint8))
+
+
+def random_codewords(enc, b0: int, B: int, seed: int, device=None) -> np.ndarray:
+    """[B][N] uint8: the codewords of random_messages(enc.K, b0, B, seed),
+    encoded on GPU `device`, or on the host when device is None."""
+    m = random_messages(enc.K, b0, B, seed)
+    return enc.encode_host(m) if device is None else enc.encode(m, device=device)
+
+
 # --- sequenced reads for the LLR-construction stage (SURVEY 8(f) row 2) -----
 DNA_FIXTURES = os.path.join(GOLDEN, "dna_fixtures.npz")
 _BASES = np.frombuffer(b"ACGT", np.uint8)

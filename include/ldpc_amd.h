@@ -329,6 +329,54 @@ int ldpc_dev_free(int32_t device, void *p);
 int ldpc_dev_memcpy(int32_t device, void *dst, const void *src, size_t bytes, int32_t kind);
 
 /* ------------------------------------------------------------------------ */
+/* Systematic encoding (the write half of the codec)                         */
+/* ------------------------------------------------------------------------ */
+/* For a graph H (M x N) with r = rank over GF(2) and K = N - r:
+ *   parity positions: scanning columns j = N-1, N-2, ..., 0, column j is a
+ *     parity position iff it is linearly independent of the parity columns
+ *     already chosen (the greedy basis in that order; r positions);
+ *   information positions: the other K columns (zero columns and duplicates
+ *     of later columns among them), message bit k at info_pos[k], ascending;
+ *   codeword: the unique c with c[info_pos[k]] = m[k] and H c = 0 (redundant
+ *     rows of H -- the DNA code has 188 -- are handled by construction).
+ * The reference ships only the pieces of an encoder (LDPC_dec/ldpc
+ * make_gen.cpp, enc.cpp: N - M message bits, dense / mixed branches commented
+ * out); the DNA code's K = 16572 = N - rank is what its file names (m1860)
+ * record.  Messages and codewords are row-major u8, one byte per bit:
+ * msg [B][K], cw [B][N] (the layout of hard_out and of d_codewords below).
+ * An encoder is immutable after create and may be shared by threads; it keeps
+ * what it needs of the graph, which may be freed. */
+typedef struct ldpc_encoder ldpc_encoder;
+
+/* Host only (GF(2) elimination), no device call.  LDPC_ERR_UNSUPPORTED when
+ * K = 0 or when the encoder's dense matrix (r x M bits) exceeds 2^31 bits. */
+ldpc_encoder *ldpc_encoder_create(const ldpc_graph *g, int *err);
+void ldpc_encoder_free(ldpc_encoder *e);
+
+/* Dimensions and positions: info_pos[K], par_pos[rank], ascending (any
+ * pointer may be NULL). */
+int ldpc_encoder_info(const ldpc_encoder *e, int32_t *N, int32_t *K, int32_t *rank, int32_t *info_pos,
+                      int32_t *par_pos);
+
+/* Encode B messages on the CPU.  A message byte other than 0 or 1 is
+ * LDPC_ERR_ARG. */
+int ldpc_encode_host(const ldpc_encoder *e, const uint8_t *msg, int64_t B, uint8_t *cw_out);
+
+/* The same on `device`, from and to host buffers (any B: the batch crosses
+ * device memory in passes).  Message bytes are checked as in
+ * ldpc_encode_host before any device call; B = 0 touches no device; without
+ * a GPU the call returns LDPC_ERR_DEVICE (ldpc_encode_host still works). */
+int ldpc_encode(const ldpc_encoder *e, const uint8_t *msg, int64_t B, uint8_t *cw_out, int32_t device);
+
+/* The same for device buffers d_msg [B][K] -> d_cw [B][N] (bit 0 of each
+ * message byte is used).  stream: a hipStream_t of `device` -- the call only
+ * enqueues and the caller's stream orders it -- or NULL: the library's own
+ * stream, and the call returns when the codewords are written.  The encoder
+ * is uploaded once per device. */
+int ldpc_encoder_encode_device(const ldpc_encoder *e, int32_t device, void *stream, const uint8_t *d_msg, int64_t B,
+                               uint8_t *d_cw);
+
+/* ------------------------------------------------------------------------ */
 /* DNA soft-input construction (the step before the decoder)                 */
 /* ------------------------------------------------------------------------ */
 /* Per-strand LLRs from read candidates -- the arithmetic of decoder.py's
