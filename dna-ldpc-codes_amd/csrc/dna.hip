@@ -22,6 +22,12 @@
 // Bit values follow DNA2binary: A=00 C=01 G=10 T=11, any other character
 // gives '2', which the count loop treats as a one (it tests == '0').
 // Arithmetic is the reference's: (double)(c0 - c1) * L, +-2 * L, +-L.
+//
+// The two ends of the strand format (code: rs_index.hpp):
+// k_rs_index_decode turns the 16-nt prefix of every raw read into its strand
+// index (the reference's rs_dec.exe, decoder.py:59-92), k_strands_write lays
+// codewords out as the strands that get synthesised (index prefix + payload,
+// the format of original files/final_DNA.txt).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +37,7 @@
 
 #include "../../include/ldpc_amd.h"
 #include "engine.hpp"
+#include "rs_index.hpp"
 
 namespace ldpc {
 namespace {
@@ -144,6 +151,100 @@ __global__ void __launch_bounds__(64) k_edit_distance(const uint8_t* __restrict_
         }
     }
     dist[p] = row[lb * 64 + lane];
+}
+
+// One read per thread: the 16-nt prefix -> (index, cnumerr), rs_index.hpp.
+// A read shorter than 16 is not touched.  No loop depends on the data; the
+// field tables are two 64-bit constants, so nothing lives in scratch.
+__global__ void __launch_bounds__(256) k_rs_index_decode(const uint8_t* __restrict__ seqs,
+                                                         const int64_t* __restrict__ off,
+                                                         const int32_t* __restrict__ len, int64_t n,
+                                                         int32_t* __restrict__ index, int32_t* __restrict__ cnumerr)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int32_t idx, ne;
+    rs::rs_read_decode(seqs + off[i], len[i], &idx, &ne);
+    index[i] = idx;
+    cnumerr[i] = ne;
+}
+
+constexpr int kStrTile = 64;     // strands per k_strands_write block (one per lane)
+constexpr int kStrChunk = 256;   // bytes of every strand per block (blockIdx.y chunks a longer strand)
+// LDS row stride of a staged strand in bytes: 64 + 1 dwords, so the 64 lanes
+// of a wave, each writing its own strand's row at the same position, fall on
+// 64 different banks
+constexpr int kStrStride = kStrChunk + 4;
+constexpr int64_t kStrMaxChunks = 65535;  // grid.y
+
+__device__ __forceinline__ uint8_t base_of_bits(uint8_t hi, uint8_t lo)
+{
+    return (uint8_t)(0x54474341u >> (8 * (2 * (hi & 1) + (lo & 1))));  // "ACGT"
+}
+
+// The transpose codewords [n_cw][N] -> strands [N][16 + n_cw / 2], grid
+// (ceil(N / 64), ceil(L / 256)), 256 threads.  Lane l owns strand j0 + l:
+// every load is one 64-byte piece of a codeword row per wave (coalesced along
+// N), wave 0 also encodes the index prefixes.  The block's tile is staged in
+// LDS and written out along the strands: when the whole strand fits a chunk
+// (the DNA code: 152 bytes) the block's 64 strands are one contiguous range
+// that starts 4-byte aligned, written as dwords.  Lanes past N load nothing
+// and their rows are never written.
+__global__ void __launch_bounds__(256) k_strands_write(const uint8_t* __restrict__ cw,
+                                                       const int32_t* __restrict__ index, int32_t n_cw, int64_t N,
+                                                       uint8_t* __restrict__ out)
+{
+    __shared__ uint32_t tile32[kStrTile * kStrStride / 4];
+    uint8_t* tile = reinterpret_cast<uint8_t*>(tile32);
+    const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
+    const int64_t j0 = (int64_t)blockIdx.x * kStrTile;
+    const int64_t j = j0 + lane;
+    const int32_t L = rs::kPrefixNt + n_cw / 2;
+    const int32_t c0 = (int32_t)blockIdx.y * kStrChunk;  // first strand byte of this chunk
+    const int32_t W = L - c0 < kStrChunk ? L - c0 : kStrChunk;
+    const int nvalid = N - j0 < kStrTile ? (int)(N - j0) : kStrTile;
+    if (c0 == 0 && wv == 0 && j < N) {
+        const uint32_t word = rs::rs_index_codeword((uint32_t)index[j]);
+#pragma unroll
+        for (int q = 0; q < rs::kPrefixNt / 4; q++) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int c = 0; c < 4; c++) v |= (uint32_t)rs::rs_prefix_base(word, 4 * q + c) << (8 * c);
+            tile32[lane * (kStrStride / 4) + q] = v;
+        }
+    }
+    for (int32_t p = (c0 == 0 ? rs::kPrefixNt : 0) + wv; p < W; p += 4) {
+        if (j < N) {
+            const size_t k = (size_t)(c0 + p - rs::kPrefixNt);  // payload base: codeword rows 2k, 2k + 1
+            const uint8_t hi = cw[(2 * k) * (size_t)N + (size_t)j];
+            const uint8_t lo = cw[(2 * k + 1) * (size_t)N + (size_t)j];
+            tile[lane * kStrStride + p] = base_of_bits(hi, lo);
+        }
+    }
+    __syncthreads();
+    const int32_t total = nvalid * W;
+    if (W == L) {
+        uint8_t* dst = out + (size_t)j0 * (size_t)L;
+        const int32_t nwords = total / 4;
+        for (int32_t f = (int32_t)threadIdx.x; f < nwords; f += 256) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const int32_t b = 4 * f + c, l = b / L;
+                v |= (uint32_t)tile[l * kStrStride + (b - l * L)] << (8 * c);
+            }
+            reinterpret_cast<uint32_t*>(dst)[f] = v;
+        }
+        for (int32_t b = 4 * nwords + (int32_t)threadIdx.x; b < total; b += 256) {
+            const int32_t l = b / L;
+            dst[b] = tile[l * kStrStride + (b - l * L)];
+        }
+    } else {
+        for (int32_t f = (int32_t)threadIdx.x; f < total; f += 256) {
+            const int32_t l = f / W, p = f - l * W;
+            out[(size_t)(j0 + l) * (size_t)L + (size_t)(c0 + p)] = tile[l * kStrStride + p];
+        }
+    }
 }
 
 struct DevBuf {
@@ -299,6 +400,162 @@ int ldpc_dna_edit_distance(const uint8_t* seqs, const int64_t* offsets, const in
                        dlen.as<int32_t>(), da.as<int32_t>(), db.as<int32_t>(), n_pairs, max_len, dd.as<int32_t>());
     LDPC_HIP(hipGetLastError());
     LDPC_HIP(hipMemcpy(dist, dd.p, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    return LDPC_OK;
+}
+
+int ldpc_dna_index_encode(const int32_t* index, int64_t n, uint8_t* prefix)
+{
+    if (n < 0 || (n > 0 && (!index || !prefix))) {
+        set_error("ldpc_dna_index_encode: bad arguments");
+        return LDPC_ERR_ARG;
+    }
+    for (int64_t i = 0; i < n; i++) {
+        if (index[i] < 0 || index[i] > 0xffff) {
+            set_error("ldpc_dna_index_encode: index " + std::to_string(i) + " is outside 0..65535");
+            return LDPC_ERR_ARG;
+        }
+    }
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t word = ldpc::rs::rs_index_codeword((uint32_t)index[i]);
+        for (int k = 0; k < ldpc::rs::kPrefixNt; k++)
+            prefix[(size_t)i * ldpc::rs::kPrefixNt + k] = ldpc::rs::rs_prefix_base(word, k);
+    }
+    return LDPC_OK;
+}
+
+// Shared argument check of the two index decoders; *total = bytes of seqs the reads span.
+static int index_decode_args(const char* who, const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths,
+                             int64_t n, const int32_t* index, const int32_t* cnumerr, int64_t* total)
+{
+    *total = 0;
+    if (n < 0 || (n > 0 && (!offsets || !lengths || !index || !cnumerr))) {
+        set_error(std::string(who) + ": bad arguments");
+        return LDPC_ERR_ARG;
+    }
+    for (int64_t i = 0; i < n; i++) {
+        if (lengths[i] < 0 || offsets[i] < 0 || offsets[i] > INT64_MAX - lengths[i]) {
+            set_error(std::string(who) + ": negative or overflowing length/offset");
+            return LDPC_ERR_ARG;
+        }
+        if (lengths[i] > 0) *total = std::max<int64_t>(*total, offsets[i] + lengths[i]);
+    }
+    if (*total > 0 && !seqs) {
+        set_error(std::string(who) + ": null sequences");
+        return LDPC_ERR_ARG;
+    }
+    return LDPC_OK;
+}
+
+int ldpc_dna_index_decode_host(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, int64_t n,
+                               int32_t* index, int32_t* cnumerr)
+{
+    int64_t total = 0;
+    if (int rc = index_decode_args("ldpc_dna_index_decode_host", seqs, offsets, lengths, n, index, cnumerr, &total))
+        return rc;
+    for (int64_t i = 0; i < n; i++)
+        ldpc::rs::rs_read_decode(lengths[i] ? seqs + offsets[i] : nullptr, lengths[i], &index[i], &cnumerr[i]);
+    return LDPC_OK;
+}
+
+int ldpc_dna_index_decode(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, int64_t n,
+                          int32_t* index, int32_t* cnumerr, int32_t device)
+{
+    using namespace ldpc;
+    int64_t total = 0;
+    if (int rc = index_decode_args("ldpc_dna_index_decode", seqs, offsets, lengths, n, index, cnumerr, &total))
+        return rc;
+    if (n == 0) return LDPC_OK;
+    if (n > (int64_t)INT32_MAX * 256) {
+        set_error("ldpc_dna_index_decode: too many reads for one call");
+        return LDPC_ERR_UNSUPPORTED;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        set_error("ldpc_dna_index_decode: no such device");
+        return LDPC_ERR_DEVICE;
+    }
+    LDPC_HIP(hipSetDevice(device));
+    DevBuf ds, doff, dlen, di, dc;
+    int rc;
+    if ((rc = dev_copy_in(ds, seqs, (size_t)total))) return rc;
+    if ((rc = dev_copy_in(doff, offsets, sizeof(int64_t) * (size_t)n))) return rc;
+    if ((rc = dev_copy_in(dlen, lengths, sizeof(int32_t) * (size_t)n))) return rc;
+    LDPC_HIP(hipMalloc(&di.p, sizeof(int32_t) * (size_t)n));
+    LDPC_HIP(hipMalloc(&dc.p, sizeof(int32_t) * (size_t)n));
+    hipLaunchKernelGGL(k_rs_index_decode, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ds.as<uint8_t>(),
+                       doff.as<int64_t>(), dlen.as<int32_t>(), n, di.as<int32_t>(), dc.as<int32_t>());
+    LDPC_HIP(hipGetLastError());
+    LDPC_HIP(hipMemcpy(index, di.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    LDPC_HIP(hipMemcpy(cnumerr, dc.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    return LDPC_OK;
+}
+
+// Shared argument check of the two strand writers.
+static int strands_args(const char* who, const uint8_t* codewords, int32_t n_cw, int64_t N, const int32_t* index,
+                        const uint8_t* out)
+{
+    if (n_cw < 2 || n_cw % 2 || N < 0 || (N > 0 && (!codewords || !index || !out))) {
+        set_error(std::string(who) + ": bad arguments (n_cw must be even and >= 2)");
+        return LDPC_ERR_ARG;
+    }
+    if (N > INT64_MAX / n_cw) {
+        set_error(std::string(who) + ": n_cw * N bytes overflow the address space");
+        return LDPC_ERR_ARG;
+    }
+    for (int64_t j = 0; j < N; j++) {
+        if (index[j] < 0 || index[j] > 0xffff) {
+            set_error(std::string(who) + ": index " + std::to_string(j) + " is outside 0..65535");
+            return LDPC_ERR_ARG;
+        }
+    }
+    return LDPC_OK;
+}
+
+int ldpc_dna_strands_host(const uint8_t* codewords, int32_t n_cw, int64_t N, const int32_t* index, uint8_t* out)
+{
+    if (int rc = strands_args("ldpc_dna_strands_host", codewords, n_cw, N, index, out)) return rc;
+    const size_t L = (size_t)ldpc::rs::kPrefixNt + (size_t)n_cw / 2;
+    for (int64_t j = 0; j < N; j++) {
+        const uint32_t word = ldpc::rs::rs_index_codeword((uint32_t)index[j]);
+        for (int k = 0; k < ldpc::rs::kPrefixNt; k++) out[(size_t)j * L + k] = ldpc::rs::rs_prefix_base(word, k);
+    }
+    // row pairs outermost: the codeword rows are read in order, once
+    for (size_t k = 0; k < (size_t)n_cw / 2; k++) {
+        const uint8_t* hi = codewords + (2 * k) * (size_t)N;
+        const uint8_t* lo = hi + (size_t)N;
+        for (int64_t j = 0; j < N; j++)
+            out[(size_t)j * L + ldpc::rs::kPrefixNt + k] = (uint8_t)("ACGT"[2 * (hi[j] & 1) + (lo[j] & 1)]);
+    }
+    return LDPC_OK;
+}
+
+int ldpc_dna_strands(const uint8_t* codewords, int32_t n_cw, int64_t N, const int32_t* index, uint8_t* out,
+                     int32_t device)
+{
+    using namespace ldpc;
+    if (int rc = strands_args("ldpc_dna_strands", codewords, n_cw, N, index, out)) return rc;
+    if (N == 0) return LDPC_OK;
+    const int64_t L = rs::kPrefixNt + n_cw / 2;
+    const int64_t chunks = (L + kStrChunk - 1) / kStrChunk;
+    if (chunks > kStrMaxChunks || N > (int64_t)INT32_MAX * kStrTile || N > INT64_MAX / L) {
+        set_error("ldpc_dna_strands: shape too large for one call");
+        return LDPC_ERR_UNSUPPORTED;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        set_error("ldpc_dna_strands: no such device");
+        return LDPC_ERR_DEVICE;
+    }
+    LDPC_HIP(hipSetDevice(device));
+    DevBuf dcw, di, dout;
+    int rc;
+    if ((rc = dev_copy_in(dcw, codewords, (size_t)n_cw * (size_t)N))) return rc;
+    if ((rc = dev_copy_in(di, index, sizeof(int32_t) * (size_t)N))) return rc;
+    LDPC_HIP(hipMalloc(&dout.p, (size_t)N * (size_t)L));
+    hipLaunchKernelGGL(k_strands_write, dim3((unsigned)((N + kStrTile - 1) / kStrTile), (unsigned)chunks), dim3(256),
+                       0, 0, dcw.as<uint8_t>(), di.as<int32_t>(), n_cw, N, dout.as<uint8_t>());
+    LDPC_HIP(hipGetLastError());
+    LDPC_HIP(hipMemcpy(out, dout.p, (size_t)N * (size_t)L, hipMemcpyDeviceToHost));
     return LDPC_OK;
 }
 

@@ -1,9 +1,12 @@
 """DNA soft-input construction: sequenced reads -> the 272 x 18432 LLR matrix
 (the step before the first decode).
 
-Host mirror of ex_decoder/decoder.py:103-519; the arithmetic runs in HIP
+Host mirror of ex_decoder/decoder.py:59-519; the arithmetic runs in HIP
 (csrc/dna.hip through the C ABI):
 
+0. raw reads are split into (decoded index, payload, quality): the first 16
+   nt are an RS(8,4) word over GF(16), decoded on the GPU; reads with more
+   than two symbol errors are dropped (decoder.py:59-92, split_reads);
 1. reads whose decoded index is not a strand index are dropped, the rest are
    grouped by strand in read order (decoder.py:103-118, a stable sort);
 2. each strand is classified (decoder.py:149-497):
@@ -116,6 +119,11 @@ def _lib():
         L.ldpc_dna_edit_distance.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, i32]
         L.ldpc_write_soft_files.argtypes = [C.c_char_p, i32, vp, vp, i32, i32]
         L.ldpc_py_float_repr.argtypes = [C.c_double, C.c_char_p, i32]
+        L.ldpc_dna_index_encode.argtypes = [vp, i64, vp]
+        L.ldpc_dna_index_decode_host.argtypes = [vp, vp, vp, i64, vp, vp]
+        L.ldpc_dna_index_decode.argtypes = [vp, vp, vp, i64, vp, vp, i32]
+        L.ldpc_dna_strands_host.argtypes = [vp, i32, i64, vp, vp]
+        L.ldpc_dna_strands.argtypes = [vp, i32, i64, vp, vp, i32]
         L._dna_bound = True
     return ldpc_amd, L
 
@@ -141,6 +149,82 @@ def edit_distance(seqs: Sequence[str], pairs: np.ndarray, device: int = 0) -> np
     mod._check(L.ldpc_dna_edit_distance(_p(buf), _p(offs), _p(lens), len(enc), _p(a), _p(b), len(pairs),
                                         _p(out), device))
     return out
+
+
+def _concat(seqs: Sequence[str]):
+    """Sequences as the C ABI takes them: concatenated bytes, offsets, lengths."""
+    enc = [s.encode("latin-1", "replace") for s in seqs]
+    lens = np.array([len(b) for b in enc], np.int32)
+    offs = np.zeros(len(enc), np.int64)
+    if len(enc) > 1:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+    buf = np.frombuffer(b"".join(enc) or b"\0", np.uint8).copy()
+    return buf, offs, lens
+
+
+# --- the strand index code: RS(8,4) over GF(16) in the 16-nt prefix ---------
+PREFIX_NT = 16            # decoder.py:60 (RS_seq[i][0:16])
+
+
+def encode_indices(index) -> np.ndarray:
+    """[n][16] uint8 ASCII: the prefix (index + RS parity) of each 16-bit
+    strand index (host; csrc/rs_index.hpp)."""
+    mod, L = _lib()
+    idx = np.asarray(index)
+    if idx.size and (idx.min() < 0 or idx.max() > 0xFFFF):
+        raise ValueError("strand indices are 16-bit values (0..65535)")
+    idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+    out = np.zeros((len(idx), PREFIX_NT), np.uint8)
+    mod._check(L.ldpc_dna_index_encode(_p(idx), len(idx), _p(out)))
+    return out
+
+
+def _decode_indices(seqs: Sequence[str], device: Optional[int]):
+    mod, L = _lib()
+    buf, offs, lens = _concat(seqs)
+    n = len(lens)
+    index = np.full(n, -1, np.int32)
+    cnumerr = np.full(n, -1, np.int32)
+    if device is None:
+        mod._check(L.ldpc_dna_index_decode_host(_p(buf), _p(offs), _p(lens), n, _p(index), _p(cnumerr)))
+    else:
+        mod._check(L.ldpc_dna_index_decode(_p(buf), _p(offs), _p(lens), n, _p(index), _p(cnumerr), device))
+    return index, cnumerr
+
+
+def decode_indices(seqs: Sequence[str], device: int = 0):
+    """(index, cnumerr), int32 [n]: the RS(8,4) decode of every raw read's
+    first 16 nt on the GPU (the reference's rs_dec.exe, decoder.py:59-80).
+    cnumerr is the number of corrected symbols (0, 1, 2) or -1, index the
+    corrected 16-bit value or -1; reads shorter than 16 nt or with a non-ACGT
+    character in the prefix give -1."""
+    return _decode_indices(seqs, device)
+
+
+def decode_indices_host(seqs: Sequence[str]):
+    """decode_indices on the CPU (one thread)."""
+    return _decode_indices(seqs, None)
+
+
+def split_reads(raw_seqs: Sequence[str], quals: Sequence[int], device: int = 0, host: bool = False):
+    """decoder.py:59-92: raw reads -> (index values, payloads, qualities) of
+    the reads whose prefix decodes (cnumerr 0, 1 or 2), in input order; the
+    payload is seq[16:].  The triple is what plan_llr / build_llr take (the
+    valid-index filter of decoder.py:110-115 is applied there)."""
+    return split_reads_counted(raw_seqs, quals, device, host)[0]
+
+
+def split_reads_counted(raw_seqs: Sequence[str], quals: Sequence[int], device: int = 0, host: bool = False):
+    """split_reads plus the histogram of cnumerr over all reads:
+    (reads, {-1: dropped, 0: .., 1: .., 2: ..})."""
+    if len(raw_seqs) != len(quals):
+        raise ValueError("raw_seqs and quals must have the same length")
+    index, cnumerr = _decode_indices(raw_seqs, None if host else device)
+    keep = np.nonzero(cnumerr >= 0)[0]
+    hist = {k: int((cnumerr == k).sum()) for k in (-1, 0, 1, 2)}
+    reads = (index[keep].astype(np.int64).tolist(), [raw_seqs[i][PREFIX_NT:] for i in keep],
+             [int(quals[i]) for i in keep])
+    return reads, hist
 
 
 def py_float_repr(v: float) -> str:

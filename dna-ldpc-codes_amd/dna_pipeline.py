@@ -139,6 +139,41 @@ def trial_from_reads(reads, codewords: np.ndarray, eps: float = 0.02, max_iter: 
     return res
 
 
+def read_trial_files(directory: str, rs: int, trial: int):
+    """(raw_seqs, quals) of one trial's <rs>_RS_<trial>.txt and
+    <rs>_RS_Q_<trial>.txt (decoder.py:48-54, :90; def_func.file_read): one
+    read per line with the '\\n' stripped, quality = ord of the line's
+    character."""
+    import os
+
+    def lines(name):
+        with open(os.path.join(directory, name), "r") as f:
+            return [ln.strip("\n") for ln in f]
+
+    seqs = lines("%d_RS_%d.txt" % (rs, trial))
+    qual = lines("%d_RS_Q_%d.txt" % (rs, trial))
+    if len(seqs) != len(qual):
+        raise ValueError(f"{len(seqs)} reads but {len(qual)} qualities")
+    return seqs, [ord(q) for q in qual]  # ord() of a line that is not one character raises, as in the reference
+
+
+def trial_from_raw_reads(raw_reads, codewords: np.ndarray, eps: float = 0.02, max_iter: int = 200, align_fn=None,
+                         decode_fn: Optional[DecodeFn] = None, faithful: bool = True, device: int = 0,
+                         host_index: bool = False) -> Dict:
+    """decoder.py:59-664 for one trial: raw reads (sequences, qualities) ->
+    index decode on the GPU (dna_llr.split_reads; host_index=True: on the CPU)
+    -> trial_from_reads.  Adds the index stage's time, the number of reads it
+    dropped and the histogram of cnumerr."""
+    import dna_llr
+    t0 = time.perf_counter()
+    reads, hist = dna_llr.split_reads_counted(*raw_reads, device=device, host=host_index)
+    t_index = time.perf_counter() - t0
+    res = trial_from_reads(reads, codewords, eps=eps, max_iter=max_iter, align_fn=align_fn, decode_fn=decode_fn,
+                           faithful=faithful, device=device)
+    res.update(t_index_s=t_index, n_reads_dropped=hist[-1], cnumerr_hist=hist)
+    return res
+
+
 def report(res: Dict, rs: int = 72000, total_time: Optional[float] = None, threshold: Optional[int] = None,
            newline: str = "\n") -> str:
     """The o_/x_ result-file body (decoder.py:668-727).  total_time adds the

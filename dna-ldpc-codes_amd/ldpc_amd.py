@@ -138,6 +138,8 @@ EXPORTS = [
     "ldpc_dev_memcpy", "ldpc_host_alloc", "ldpc_host_free", "ldpc_dna_llr", "ldpc_dna_llr_codes", "ldpc_dna_edit_distance", "ldpc_write_soft_files", "ldpc_py_float_repr",
     "ldpc_encoder_create", "ldpc_encoder_free", "ldpc_encoder_info", "ldpc_encode_host", "ldpc_encode",
     "ldpc_encoder_encode_device",
+    "ldpc_dna_index_encode", "ldpc_dna_index_decode_host", "ldpc_dna_index_decode", "ldpc_dna_strands_host",
+    "ldpc_dna_strands",
 ]
 
 

@@ -184,6 +184,66 @@ def dna_reads(codewords: np.ndarray, seed: int = 0, n_reads: int = 72000, sub: f
     return idx.tolist(), seqs, quals.tolist()
 
 
+def dna_strands(codewords: np.ndarray, index=None, device=None) -> np.ndarray:
+    """[N][16 + n_cw/2] uint8 ASCII: the strands to synthesise -- strand j =
+    the 16-nt prefix of index[j] (index + RS(8,4) parity, dna_llr.encode_indices)
+    followed by strand_payloads(codewords)[j]; the format of the reference's
+    original files/final_DNA.txt.  index defaults to dna_llr.strand_indices();
+    written on GPU `device`, or on the host when device is None."""
+    import ctypes as C
+    import dna_llr
+    mod, L = dna_llr._lib()
+    cw = np.ascontiguousarray(codewords, np.uint8)
+    if cw.ndim != 2 or cw.shape[0] < 2 or cw.shape[0] % 2:
+        raise ValueError("codewords come in nucleotide pairs (bits 2k, 2k+1 of a strand)")
+    n_cw, N = cw.shape
+    idx = np.asarray(dna_llr.strand_indices() if index is None else index)
+    if idx.shape != (N,):
+        raise ValueError(f"{N} strands need {N} index values")
+    if idx.size and (idx.min() < 0 or idx.max() > 0xFFFF):
+        raise ValueError("strand indices are 16-bit values (0..65535)")
+    idx = np.ascontiguousarray(idx, np.int32)
+    out = np.zeros((N, 16 + n_cw // 2), np.uint8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    if device is None:
+        mod._check(L.ldpc_dna_strands_host(p(cw), n_cw, N, p(idx), p(out)))
+    else:
+        mod._check(L.ldpc_dna_strands(p(cw), n_cw, N, p(idx), p(out), device))
+    return out
+
+
+def dna_raw_reads(codewords: np.ndarray, seed: int = 0, n_reads: int = 72000, sub: float = 0.01,
+                  ins: float = 0.0, dele: float = 0.0, quality: np.ndarray = None):
+    """Simulated raw reads, before index decoding: (sequences, qualities) --
+    the content of <rs>_RS_<t>.txt / <rs>_RS_Q_<t>.txt.  As dna_reads, but
+    whole strands (dna_strands: prefix + payload) are sampled and the channel's
+    substitutions / insertions / deletions fall on every position, the index
+    prefix included."""
+    rng = np.random.default_rng(seed)
+    strands = dna_strands(codewords)
+    N, nt = strands.shape
+    strand = rng.integers(0, N, n_reads)
+    qh = quality_hist() if quality is None else quality
+    qvals = np.nonzero(qh)[0]
+    quals = rng.choice(qvals, n_reads, p=qh[qvals] / qh[qvals].sum()).astype(np.int64)
+    r = strands[strand].copy()
+    m = rng.random(r.shape) < sub
+    r[m] = _BASES[(np.searchsorted(_BASES, r[m]) + rng.integers(1, 4, int(m.sum()))) % 4]
+    seqs = [row.tobytes().decode() for row in r]
+    if ins > 0 or dele > 0:
+        n_ins = rng.binomial(nt, ins, n_reads)
+        n_del = rng.binomial(nt, dele, n_reads)
+        for k in np.nonzero((n_ins > 0) | (n_del > 0))[0]:
+            s = list(seqs[k])
+            for _ in range(int(n_del[k])):
+                if s:
+                    del s[int(rng.integers(0, len(s)))]
+            for _ in range(int(n_ins[k])):
+                s.insert(int(rng.integers(0, len(s) + 1)), "ACGT"[int(rng.integers(0, 4))])
+            seqs[k] = "".join(s)
+    return seqs, quals.tolist()
+
+
 def dna_reads_edge_cases(codewords: np.ndarray, reads, seed: int = 1):
     """Append reads that put the rarer per-strand shapes of decoder.py's loop
     on fresh strands: single short read (q > 63 and q <= 63), single long

@@ -412,6 +412,39 @@ int ldpc_dna_edit_distance(const uint8_t *seqs, const int64_t *offsets, const in
                            const int32_t *pair_a, const int32_t *pair_b, int64_t n_pairs, int32_t *dist,
                            int32_t device);
 
+/* The strand index code: every strand starts with a
+ * 16-nt prefix, the 16-bit strand index and 16 parity bits as one word of the
+ * systematic RS(8,4) code over GF(16) (primitive polynomial 19, generator
+ * roots alpha^1..alpha^4, index symbols first; two bases per symbol,
+ * A/C/G/T = 0..3, high pair first -- the format of original
+ * files/final_DNA.txt).
+ *
+ * ldpc_dna_index_encode: prefix[n][16] ASCII for n index values, on the host;
+ * an index outside 0..65535 is LDPC_ERR_ARG. */
+int ldpc_dna_index_encode(const int32_t *index, int64_t n, uint8_t *prefix);
+
+/* Decode the prefix of n raw reads (the reference's rs_dec.exe step,
+ * decoder.py:59-92).  Read i is seqs[offsets[i] .. offsets[i]+lengths[i]), as
+ * in ldpc_dna_edit_distance; only its first 16 bytes are used.  If a codeword
+ * lies within two symbol errors of the prefix, cnumerr[i] is that number (0,
+ * 1 or 2) and index[i] the corrected index; otherwise, and for a read shorter
+ * than 16 or with a character other than A, C, G, T in the prefix, both are
+ * -1.  The _host form runs on the CPU; the other passes the host buffers
+ * through `device` (n = 0 does nothing and needs no device). */
+int ldpc_dna_index_decode_host(const uint8_t *seqs, const int64_t *offsets, const int32_t *lengths, int64_t n,
+                               int32_t *index, int32_t *cnumerr);
+int ldpc_dna_index_decode(const uint8_t *seqs, const int64_t *offsets, const int32_t *lengths, int64_t n,
+                          int32_t *index, int32_t *cnumerr, int32_t device);
+
+/* The strands to synthesise: codewords [n_cw][N] u8 (n_cw even, >= 2; bit 0
+ * of each byte is used) and index[N] (0..65535) -> out [N][16 + n_cw/2] ASCII
+ * without separators: strand j = the prefix of index[j], then base k from
+ * bits (2k, 2k+1) of column j (A/C/G/T = 00/01/10/11).  Host form and, with
+ * host buffers, on `device`. */
+int ldpc_dna_strands_host(const uint8_t *codewords, int32_t n_cw, int64_t N, const int32_t *index, uint8_t *out);
+int ldpc_dna_strands(const uint8_t *codewords, int32_t n_cw, int64_t N, const int32_t *index, uint8_t *out,
+                     int32_t device);
+
 /* Write soft<rs>_n18432_m1860_<i+1>.txt, i < n_files, into dir: row i of
  * llr as str(value)+' ' tokens (decoder.py:511-516, def_func.py:54-57);
  * int_mask (may be NULL) marks the int-0 entries.  Host only. */
