@@ -1,7 +1,8 @@
 // dna.hip -- the step before the decoder: per-strand
 // read candidates -> the 272 x 18432 LLR matrix the first decode consumes,
 // plus the pairwise edit distances that pick which ragged candidates go to
-// the aligner.
+// the aligner, and the aligner itself (the centre-star alignment of
+// star_align.hpp, DESIGN.md sec. 8.6: k_star_align_pairs).
 //
 // Reference: ex_decoder/decoder.py:142-519 (the strand loop; count rule
 // :266-320 and :442-497), def_func.py:10-26 (edit_dist), :97-117
@@ -32,12 +33,14 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/ldpc_amd.h"
 #include "engine.hpp"
 #include "rs_index.hpp"
+#include "star_align.hpp"
 
 namespace ldpc {
 namespace {
@@ -151,6 +154,72 @@ __global__ void __launch_bounds__(64) k_edit_distance(const uint8_t* __restrict_
         }
     }
     dist[p] = row[lb * 64 + lane];
+}
+
+// The pairwise step of the centre-star alignment (star_align.hpp, DESIGN.md
+// sec. 8.6): one (read, centre) pair per lane, blocks of up to 64 pairs laid
+// out by the host (pairs blk_first[b] .. blk_first[b + 1] belong to block b).
+// The lane fills its Levenshtein table row by row as k_edit_distance does (DP
+// row and centre lane-interleaved in LDS) and records every cell's traceback
+// move, 2 bits, 16 cells per word: word q of table row i of lane l is
+// ws[blk_ws[b] + ((i - 1) * blk_wpr[b] + q) * 64 + l], so the 64 lanes' stores
+// of one word are one contiguous 256-byte piece.  The host sizes the block's
+// piece of ws from the lengths it checked: rows <= the block's longest read,
+// blk_wpr[b] >= ceil(n / 16) for every pair of the block.  The same lane then
+// walks its moves back from (m, n) (star::walk: at most m + n steps, every
+// index bounded by m and n whatever ws holds) and writes the pair's script:
+// at[n] at at_off[p], cnt[n + 1] at at_off[p] + p, the inserted bytes
+// end-justified in ins[ins_off[p] .. ins_off[p] + m), and the distance.
+__global__ void __launch_bounds__(64) k_star_align_pairs(
+    const uint8_t* __restrict__ seqs, const int64_t* __restrict__ off, const int32_t* __restrict__ len,
+    const int32_t* __restrict__ pr, const int32_t* __restrict__ pc, const int64_t* __restrict__ blk_first,
+    const int64_t* __restrict__ blk_ws, const int32_t* __restrict__ blk_wpr, const int64_t* __restrict__ at_off,
+    const int64_t* __restrict__ ins_off, int64_t blk0, int32_t max_n, uint32_t* ws, uint8_t* __restrict__ at,
+    int32_t* __restrict__ cnt, uint8_t* __restrict__ ins, int32_t* __restrict__ dist)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t star_smem[];
+    const int lane = threadIdx.x;
+    uint16_t* row = reinterpret_cast<uint16_t*>(star_smem);
+    uint8_t* cs = star_smem + sizeof(uint16_t) * 64 * (size_t)(max_n + 1);
+    const int64_t b = blk0 + blockIdx.x;
+    const int64_t p = blk_first[b] + lane;
+    if (p >= blk_first[b + 1]) return;
+    const uint8_t* r = seqs + off[pr[p]];
+    const uint8_t* c = seqs + off[pc[p]];
+    const int m = len[pr[p]], n = len[pc[p]];
+    const int64_t wpr = blk_wpr[b];
+    uint32_t* w = ws + blk_ws[b] + lane;
+    for (int j = 0; j < n; j++) cs[j * 64 + lane] = c[j];
+    for (int j = 0; j <= n; j++) row[j * 64 + lane] = (uint16_t)j;
+    for (int i = 1; i <= m; i++) {
+        const uint8_t ri = r[i - 1];
+        uint32_t diag = row[lane];
+        row[lane] = (uint16_t)i;
+        uint32_t left = (uint32_t)i, word = 0;
+        uint32_t* wrow = w + (int64_t)(i - 1) * wpr * 64;
+        for (int j = 1; j <= n; j++) {
+            const uint32_t up = row[j * 64 + lane];
+            const uint32_t sub = diag + (ri != cs[(j - 1) * 64 + lane] ? 1u : 0u);
+            const uint32_t v = min(sub, min(up, left) + 1u);
+            const uint32_t mv = v == sub ? (uint32_t)star::kDiag : v == up + 1u ? (uint32_t)star::kUp
+                                                                                : (uint32_t)star::kLeft;
+            word |= mv << (2 * ((j - 1) & 15));
+            if ((j & 15) == 0 || j == n) {
+                wrow[(int64_t)((j - 1) >> 4) * 64] = word;
+                word = 0;
+            }
+            row[j * 64 + lane] = (uint16_t)v;
+            diag = up;
+            left = v;
+        }
+    }
+    dist[p] = row[n * 64 + lane];
+    star::walk(
+        r, (int64_t)m, (int64_t)n,
+        [w, wpr](int64_t i, int64_t j) {
+            return (w[((i - 1) * wpr + ((j - 1) >> 4)) * 64] >> (2 * ((j - 1) & 15))) & 3u;
+        },
+        at + at_off[p], cnt + at_off[p] + p, ins + ins_off[p]);
 }
 
 // One read per thread: the 16-nt prefix -> (index, cnumerr), rs_index.hpp.
@@ -557,6 +626,398 @@ int ldpc_dna_strands(const uint8_t* codewords, int32_t n_cw, int64_t N, const in
     LDPC_HIP(hipGetLastError());
     LDPC_HIP(hipMemcpy(out, dout.p, (size_t)N * (size_t)L, hipMemcpyDeviceToHost));
     return LDPC_OK;
+}
+
+}  // extern "C"
+
+// --- the centre-star alignment (star_align.hpp) ---------
+namespace {
+
+namespace star = ldpc::star;
+
+constexpr int32_t kStarMaxLen = 800;               // device path: the DP row and the centre of 64 lanes in LDS
+constexpr int64_t kStarMaxGroup = 32768;           // reads per group (the host keeps a k x k distance matrix)
+constexpr int64_t kStarDefaultWs = 256ll << 20;    // workspace_bytes = 0
+
+struct StarCall {
+    const uint8_t* seqs;
+    const int64_t* offsets;
+    const int32_t* lengths;
+    int64_t n_seqs;
+    const int64_t* group_ptr;
+    int64_t n_groups;
+    int32_t* center;
+    int32_t* width;
+    int64_t* out_ptr;
+    uint8_t* out;
+    int64_t out_capacity;
+    int64_t* out_needed;
+    int32_t* dist;
+};
+
+// What both entry points gather before the merge: the centre of every group
+// (index inside the group), and per sequence its script and distance to the centre.
+struct StarScripts {
+    std::vector<int64_t> centre;
+    std::vector<star::RowScript> rows;
+    std::vector<int32_t> dist;
+    std::vector<star::Script> host;  // the scripts made on the host, by sequence
+};
+
+int star_args(const std::string& who, const StarCall& a)
+{
+    if (a.n_seqs < 0 || a.n_groups < 0 || a.out_capacity < 0 || (a.n_seqs > 0 && (!a.offsets || !a.lengths)) ||
+        (a.n_groups > 0 && (!a.group_ptr || !a.center || !a.width || !a.out_ptr)) || (a.out_capacity > 0 && !a.out)) {
+        set_error(who + ": bad arguments");
+        return LDPC_ERR_ARG;
+    }
+    if (a.out_needed) *a.out_needed = 0;
+    int64_t total = 0;
+    for (int64_t i = 0; i < a.n_seqs; i++) {
+        if (a.lengths[i] < 0 || a.offsets[i] < 0 || a.offsets[i] > INT64_MAX - a.lengths[i]) {
+            set_error(who + ": negative or overflowing length/offset");
+            return LDPC_ERR_ARG;
+        }
+        if (a.lengths[i] > 0) total = std::max<int64_t>(total, a.offsets[i] + a.lengths[i]);
+    }
+    if (total > 0 && !a.seqs) {
+        set_error(who + ": null sequences");
+        return LDPC_ERR_ARG;
+    }
+    if (a.n_groups == 0 ? a.n_seqs != 0 : (a.group_ptr[0] != 0 || a.group_ptr[a.n_groups] != a.n_seqs)) {
+        set_error(who + ": group_ptr must run from 0 to n_seqs");
+        return LDPC_ERR_ARG;
+    }
+    for (int64_t g = 0; g < a.n_groups; g++) {
+        if (a.group_ptr[g + 1] < a.group_ptr[g] || a.group_ptr[g + 1] > a.n_seqs) {
+            set_error(who + ": group_ptr is not monotone");
+            return LDPC_ERR_ARG;
+        }
+        if (a.group_ptr[g + 1] - a.group_ptr[g] > kStarMaxGroup) {
+            set_error(who + ": more than " + std::to_string(kStarMaxGroup) + " reads in one group");
+            return LDPC_ERR_ARG;
+        }
+    }
+    return LDPC_OK;
+}
+
+const uint8_t* star_seq(const StarCall& a, int64_t i) { return a.lengths[i] ? a.seqs + a.offsets[i] : nullptr; }
+
+// One group on the host (star::group_scripts) into s.
+void star_group_host(const StarCall& a, int64_t g, StarScripts* s)
+{
+    const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
+    if (k == 0) return;
+    std::vector<const uint8_t*> rd((size_t)k);
+    std::vector<int64_t> ln((size_t)k);
+    for (int64_t q = 0; q < k; q++) {
+        rd[(size_t)q] = star_seq(a, g0 + q);
+        ln[(size_t)q] = a.lengths[g0 + q];
+    }
+    s->centre[(size_t)g] = star::group_scripts(rd.data(), ln.data(), k, s->host.data() + g0);
+    for (int64_t q = 0; q < k; q++) {
+        const star::Script& sc = s->host[(size_t)(g0 + q)];
+        s->rows[(size_t)(g0 + q)] = star::RowScript{sc.at.data(), sc.cnt.data(), sc.ins.data()};
+        s->dist[(size_t)(g0 + q)] = (int32_t)sc.dist;
+    }
+}
+
+// The merge: widths and out_ptr first, then (if the buffer holds them) the rows.
+int star_finish(const std::string& who, const StarCall& a, const StarScripts& s)
+{
+    std::vector<int32_t> w;
+    int64_t total = 0;
+    for (int64_t g = 0; g < a.n_groups; g++) {
+        const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
+        a.out_ptr[g] = total;
+        a.center[g] = k ? (int32_t)s.centre[(size_t)g] : -1;
+        a.width[g] = 0;
+        if (k == 0) continue;
+        const int64_t n = a.lengths[g0 + s.centre[(size_t)g]];
+        const int64_t wd = star::merge_width(s.rows.data() + g0, k, s.centre[(size_t)g], n, &w);
+        if (wd > INT32_MAX || (wd > 0 && k > (INT64_MAX - total) / wd)) {
+            set_error(who + ": the aligned rows overflow the output sizes");
+            return LDPC_ERR_ARG;
+        }
+        a.width[g] = (int32_t)wd;
+        total += k * wd;
+    }
+    if (a.n_groups > 0) a.out_ptr[a.n_groups] = total;
+    if (a.out_needed) *a.out_needed = total;
+    if (a.dist) std::copy(s.dist.begin(), s.dist.end(), a.dist);
+    if (total > a.out_capacity) {
+        set_error(who + ": the output buffer holds " + std::to_string(a.out_capacity) + " bytes, the rows need " +
+                  std::to_string(total));
+        return LDPC_ERR_ARG;
+    }
+    for (int64_t g = 0; g < a.n_groups; g++) {
+        const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
+        if (k == 0) continue;
+        const int64_t c = s.centre[(size_t)g], n = a.lengths[g0 + c];
+        const int64_t wd = star::merge_width(s.rows.data() + g0, k, c, n, &w);
+        star::merge_rows(s.rows.data() + g0, k, c, star_seq(a, g0 + c), n, w, wd, a.out + a.out_ptr[g]);
+    }
+    return LDPC_OK;
+}
+
+void star_scripts_init(const StarCall& a, StarScripts* s)
+{
+    s->centre.assign((size_t)a.n_groups, 0);
+    s->rows.assign((size_t)a.n_seqs, star::RowScript());
+    s->dist.assign((size_t)a.n_seqs, 0);
+    s->host.assign((size_t)a.n_seqs, star::Script());
+}
+
+int star_align_host(const StarCall& a)
+{
+    const std::string who = "ldpc_dna_star_align_host";
+    if (int rc = star_args(who, a)) return rc;
+    StarScripts s;
+    star_scripts_init(a, &s);
+    for (int64_t g = 0; g < a.n_groups; g++) star_group_host(a, g, &s);
+    return star_finish(who, a, s);
+}
+
+// Workspace words of one lane-interleaved block: rows x words per row x 64 lanes.
+int64_t star_block_words(int64_t m, int64_t wpr) { return m * wpr * 64; }
+
+int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes, int64_t* stats)
+{
+    using namespace ldpc;
+    const std::string who = "ldpc_dna_star_align";
+    if (stats) stats[0] = stats[1] = stats[2] = 0;
+    if (int rc = star_args(who, a)) return rc;
+    if (workspace_bytes < 0) {
+        set_error(who + ": negative workspace_bytes");
+        return LDPC_ERR_ARG;
+    }
+    if (a.n_seqs > INT32_MAX) {
+        set_error(who + ": too many sequences for one call");
+        return LDPC_ERR_UNSUPPORTED;
+    }
+    StarScripts s;
+    star_scripts_init(a, &s);
+    if (a.n_groups == 0) return star_finish(who, a, s);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        set_error(who + ": no such device");
+        return LDPC_ERR_DEVICE;
+    }
+    LDPC_HIP(hipSetDevice(device));
+    const int64_t budget_words = (workspace_bytes ? workspace_bytes : kStarDefaultWs) / 4;
+
+    // groups the device takes: two reads or more, none longer than kStarMaxLen
+    std::vector<uint8_t> on_dev((size_t)a.n_groups, 0);
+    int64_t seq_bytes = 0, n_dist_pairs = 0;
+    int32_t max_len = 0;
+    for (int64_t g = 0; g < a.n_groups; g++) {
+        const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
+        bool ok = k >= 2;
+        for (int64_t q = g0; q < g0 + k && ok; q++) ok = a.lengths[q] <= kStarMaxLen;
+        on_dev[(size_t)g] = ok;
+        if (!ok) continue;
+        for (int64_t q = g0; q < g0 + k; q++) {
+            max_len = std::max(max_len, a.lengths[q]);
+            if (a.lengths[q]) seq_bytes = std::max<int64_t>(seq_bytes, a.offsets[q] + a.lengths[q]);
+        }
+        if (k > 2) n_dist_pairs += k * (k - 1) / 2;
+    }
+    DevBuf ds, doff, dlen;
+    int rc;
+    if ((rc = dev_copy_in(ds, a.seqs, (size_t)seq_bytes))) return rc;
+    if ((rc = dev_copy_in(doff, a.offsets, sizeof(int64_t) * (size_t)a.n_seqs))) return rc;
+    if ((rc = dev_copy_in(dlen, a.lengths, sizeof(int32_t) * (size_t)a.n_seqs))) return rc;
+
+    // the centres: k_edit_distance on all in-group pairs (k = 2: the tie goes to read 0)
+    if (n_dist_pairs > 0) {
+        std::vector<int32_t> pa((size_t)n_dist_pairs), pb((size_t)n_dist_pairs), d((size_t)n_dist_pairs);
+        int64_t np = 0;
+        for (int64_t g = 0; g < a.n_groups; g++) {
+            const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
+            if (!on_dev[(size_t)g] || k <= 2) continue;
+            for (int64_t x = 0; x < k; x++)
+                for (int64_t y = x + 1; y < k; y++, np++) {
+                    pa[(size_t)np] = (int32_t)(g0 + x);
+                    pb[(size_t)np] = (int32_t)(g0 + y);
+                }
+        }
+        DevBuf da, db, dd;
+        if ((rc = dev_copy_in(da, pa.data(), sizeof(int32_t) * (size_t)np))) return rc;
+        if ((rc = dev_copy_in(db, pb.data(), sizeof(int32_t) * (size_t)np))) return rc;
+        LDPC_HIP(hipMalloc(&dd.p, sizeof(int32_t) * (size_t)np));
+        const size_t lds = (sizeof(uint16_t) * (size_t)(max_len + 1) + (size_t)max_len) * 64;
+        hipLaunchKernelGGL(k_edit_distance, dim3((unsigned)((np + 63) / 64)), dim3(64), lds, 0, ds.as<uint8_t>(),
+                           doff.as<int64_t>(), dlen.as<int32_t>(), da.as<int32_t>(), db.as<int32_t>(), np, max_len,
+                           dd.as<int32_t>());
+        LDPC_HIP(hipGetLastError());
+        LDPC_HIP(hipMemcpy(d.data(), dd.p, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost));
+        np = 0;
+        std::vector<int64_t> dm;
+        for (int64_t g = 0; g < a.n_groups; g++) {
+            const int64_t k = a.group_ptr[g + 1] - a.group_ptr[g];
+            if (!on_dev[(size_t)g] || k <= 2) continue;
+            dm.assign((size_t)(k * k), 0);
+            for (int64_t x = 0; x < k; x++)
+                for (int64_t y = x + 1; y < k; y++, np++) dm[(size_t)(x * k + y)] = dm[(size_t)(y * k + x)] = d[(size_t)np];
+            s.centre[(size_t)g] = star::choose_centre(dm.data(), k);
+        }
+    }
+
+    // a group with a pair whose own block (64 lanes x m rows x ceil(n / 16) words) is
+    // beyond the budget goes to the host
+    for (int64_t g = 0; g < a.n_groups; g++) {
+        if (!on_dev[(size_t)g]) continue;
+        const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
+        const int64_t wpr = ((int64_t)a.lengths[g0 + s.centre[(size_t)g]] + 15) / 16;
+        for (int64_t q = g0; q < g0 + k; q++)
+            if (q != g0 + s.centre[(size_t)g] && star_block_words(a.lengths[q], wpr) > budget_words) on_dev[(size_t)g] = 0;
+    }
+
+    // the (read, centre) pairs, cut into blocks of at most 64 that fit the budget
+    std::vector<int32_t> pr, pc, blk_wpr;
+    std::vector<int64_t> at_off, ins_off, blk_first, blk_words;
+    int64_t at_total = 0, ins_total = 0, n_host = 0;
+    int32_t max_n = 0;
+    {
+        int64_t cnt = 0, bm = 0, bw = 0;
+        for (int64_t g = 0; g < a.n_groups; g++) {
+            const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
+            if (!on_dev[(size_t)g]) {
+                if (k >= 2) n_host++;
+                continue;
+            }
+            const int64_t c = g0 + s.centre[(size_t)g], n = a.lengths[c], wpr = (n + 15) / 16;
+            max_n = std::max(max_n, (int32_t)n);
+            for (int64_t q = g0; q < g0 + k; q++) {
+                if (q == c) continue;
+                const int64_t m = a.lengths[q];
+                if (cnt == 64 || (cnt > 0 && star_block_words(std::max(bm, m), std::max(bw, wpr)) > budget_words)) {
+                    blk_words.push_back(star_block_words(bm, bw));
+                    blk_wpr.push_back((int32_t)bw);
+                    cnt = bm = bw = 0;
+                }
+                if (cnt == 0) blk_first.push_back((int64_t)pr.size());
+                cnt++;
+                bm = std::max(bm, m);
+                bw = std::max(bw, wpr);
+                pr.push_back((int32_t)q);
+                pc.push_back((int32_t)c);
+                at_off.push_back(at_total);
+                ins_off.push_back(ins_total);
+                at_total += n;
+                ins_total += m;
+            }
+        }
+        if (cnt > 0) {
+            blk_words.push_back(star_block_words(bm, bw));
+            blk_wpr.push_back((int32_t)bw);
+        }
+        blk_first.push_back((int64_t)pr.size());
+    }
+    const int64_t P = (int64_t)pr.size(), NB = (int64_t)blk_words.size();
+    std::vector<uint8_t> h_at((size_t)at_total), h_ins((size_t)ins_total);
+    std::vector<int32_t> h_cnt((size_t)(at_total + P)), h_dist((size_t)P);
+    int64_t passes = 0;
+    if (P > 0) {
+        // the passes: runs of blocks whose pieces of the workspace fit the budget together
+        std::vector<int64_t> blk_ws((size_t)NB), pass_first;
+        int64_t acc = 0, ws_words = 0;
+        for (int64_t b = 0; b < NB; b++) {
+            if (b == 0 || acc + blk_words[(size_t)b] > budget_words) {
+                pass_first.push_back(b);
+                acc = 0;
+            }
+            blk_ws[(size_t)b] = acc;
+            acc += blk_words[(size_t)b];
+            ws_words = std::max(ws_words, acc);
+        }
+        pass_first.push_back(NB);
+        passes = (int64_t)pass_first.size() - 1;
+        DevBuf dpr, dpc, dbf, dbw, dbp, dao, dio, dws, dat, dcnt, dins, ddist;
+        if ((rc = dev_copy_in(dpr, pr.data(), sizeof(int32_t) * (size_t)P))) return rc;
+        if ((rc = dev_copy_in(dpc, pc.data(), sizeof(int32_t) * (size_t)P))) return rc;
+        if ((rc = dev_copy_in(dbf, blk_first.data(), sizeof(int64_t) * (size_t)(NB + 1)))) return rc;
+        if ((rc = dev_copy_in(dbw, blk_ws.data(), sizeof(int64_t) * (size_t)NB))) return rc;
+        if ((rc = dev_copy_in(dbp, blk_wpr.data(), sizeof(int32_t) * (size_t)NB))) return rc;
+        if ((rc = dev_copy_in(dao, at_off.data(), sizeof(int64_t) * (size_t)P))) return rc;
+        if ((rc = dev_copy_in(dio, ins_off.data(), sizeof(int64_t) * (size_t)P))) return rc;
+        LDPC_HIP(hipMalloc(&dws.p, std::max<size_t>(sizeof(uint32_t) * (size_t)ws_words, 16)));
+        LDPC_HIP(hipMalloc(&dat.p, std::max<size_t>((size_t)at_total, 16)));
+        LDPC_HIP(hipMalloc(&dcnt.p, sizeof(int32_t) * (size_t)(at_total + P)));
+        LDPC_HIP(hipMalloc(&dins.p, std::max<size_t>((size_t)ins_total, 16)));
+        LDPC_HIP(hipMalloc(&ddist.p, sizeof(int32_t) * (size_t)P));
+        const size_t lds = (sizeof(uint16_t) * (size_t)(max_n + 1) + (size_t)max_n) * 64;
+        for (int64_t q = 0; q < passes; q++) {
+            const int64_t b0 = pass_first[(size_t)q], nb = pass_first[(size_t)q + 1] - b0;
+            hipLaunchKernelGGL(k_star_align_pairs, dim3((unsigned)nb), dim3(64), lds, 0, ds.as<uint8_t>(),
+                               doff.as<int64_t>(), dlen.as<int32_t>(), dpr.as<int32_t>(), dpc.as<int32_t>(),
+                               dbf.as<int64_t>(), dbw.as<int64_t>(), dbp.as<int32_t>(), dao.as<int64_t>(),
+                               dio.as<int64_t>(), b0, max_n, dws.as<uint32_t>(), dat.as<uint8_t>(), dcnt.as<int32_t>(),
+                               dins.as<uint8_t>(), ddist.as<int32_t>());
+            LDPC_HIP(hipGetLastError());
+        }
+        if (at_total) LDPC_HIP(hipMemcpy(h_at.data(), dat.p, (size_t)at_total, hipMemcpyDeviceToHost));
+        LDPC_HIP(hipMemcpy(h_cnt.data(), dcnt.p, sizeof(int32_t) * (size_t)(at_total + P), hipMemcpyDeviceToHost));
+        if (ins_total) LDPC_HIP(hipMemcpy(h_ins.data(), dins.p, (size_t)ins_total, hipMemcpyDeviceToHost));
+        LDPC_HIP(hipMemcpy(h_dist.data(), ddist.p, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost));
+    }
+    for (int64_t p = 0; p < P; p++) {
+        const int64_t q = pr[(size_t)p], m = a.lengths[q], n = a.lengths[pc[(size_t)p]];
+        const int32_t* cnt = h_cnt.data() + at_off[(size_t)p] + p;
+        int64_t t = 0;
+        bool ok = true;
+        for (int64_t j = 0; j <= n; j++) {
+            ok = ok && cnt[j] >= 0 && cnt[j] <= m;
+            t += cnt[j];
+        }
+        if (!ok || t > m) {
+            set_error(who + ": a device script is inconsistent with its read");
+            return LDPC_ERR_DEVICE;
+        }
+        s.rows[(size_t)q] = star::RowScript{h_at.data() + at_off[(size_t)p], cnt, h_ins.data() + ins_off[(size_t)p] + m - t};
+        s.dist[(size_t)q] = h_dist[(size_t)p];
+    }
+    for (int64_t g = 0; g < a.n_groups; g++)
+        if (!on_dev[(size_t)g]) star_group_host(a, g, &s);
+    if (stats) {
+        stats[0] = n_host;
+        stats[1] = passes;
+        stats[2] = P;
+    }
+    return star_finish(who, a, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_dna_star_align_host(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, int64_t n_seqs,
+                             const int64_t* group_ptr, int64_t n_groups, int32_t* center, int32_t* width,
+                             int64_t* out_ptr, uint8_t* out, int64_t out_capacity, int64_t* out_needed, int32_t* dist)
+{
+    const StarCall a{seqs, offsets, lengths, n_seqs, group_ptr, n_groups, center, width,
+                     out_ptr, out, out_capacity, out_needed, dist};
+    try {
+        return star_align_host(a);
+    } catch (const std::bad_alloc&) {
+        set_error("ldpc_dna_star_align_host: out of host memory");
+        return LDPC_ERR_DEVICE;
+    }
+}
+
+int ldpc_dna_star_align(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, int64_t n_seqs,
+                        const int64_t* group_ptr, int64_t n_groups, int32_t* center, int32_t* width, int64_t* out_ptr,
+                        uint8_t* out, int64_t out_capacity, int64_t* out_needed, int32_t* dist, int32_t device,
+                        int64_t workspace_bytes, int64_t* stats)
+{
+    const StarCall a{seqs, offsets, lengths, n_seqs, group_ptr, n_groups, center, width,
+                     out_ptr, out, out_capacity, out_needed, dist};
+    try {
+        return star_align_device(a, device, workspace_bytes, stats);
+    } catch (const std::bad_alloc&) {
+        set_error("ldpc_dna_star_align: out of host memory");
+        return LDPC_ERR_DEVICE;
+    }
 }
 
 }  // extern "C"

@@ -26,16 +26,19 @@ Host mirror of ex_decoder/decoder.py:59-519; the arithmetic runs in HIP
 Differences from the reference (deliberate): when the LAST strand holding
 reads is ragged with no close pair, or is a single short read, the reference
 keeps looping past the end of decimal_index and raises IndexError; here that
-strand simply gets the same LLRs as any other strand of its kind.  The
-aligner is injected: MUSCLE is out of scope, so the parity tests
-hand the same deterministic `pad_align` stand-in to the product and to the
-oracle.
+strand simply gets the same LLRs as any other strand of its kind.  MUSCLE is
+out of scope: the aligner is either injected (a callable; the
+older parity tests hand the same deterministic `pad_align` stand-in to the
+product and to the oracle) or the built-in centre-star alignment,
+align_fn="star" (star_align / star_align_groups), whose
+pairwise tables and tracebacks run on the GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
 import os
+import time
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence, Tuple
 
@@ -93,6 +96,8 @@ class LlrResult:
     # None when some |count difference| > 127 (no int8 code)
     codes: Optional[np.ndarray] = None  # [2*PAYLOAD_NT][S] int8
     unit: float = 0.0                   # ln((1-eps)/eps)
+    n_align_pairs: int = 0              # read-to-centre alignments of align_fn="star"
+    t_align_s: float = 0.0              # time spent in the aligner
 
     def code_table(self) -> np.ndarray:
         """table[k + 128] = k * unit: with `codes`, the input of
@@ -124,6 +129,8 @@ def _lib():
         L.ldpc_dna_index_decode.argtypes = [vp, vp, vp, i64, vp, vp, i32]
         L.ldpc_dna_strands_host.argtypes = [vp, i32, i64, vp, vp]
         L.ldpc_dna_strands.argtypes = [vp, i32, i64, vp, vp, i32]
+        L.ldpc_dna_star_align_host.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp]
+        L.ldpc_dna_star_align.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32, i64, vp]
         L._dna_bound = True
     return ldpc_amd, L
 
@@ -227,6 +234,80 @@ def split_reads_counted(raw_seqs: Sequence[str], quals: Sequence[int], device: i
     return reads, hist
 
 
+# --- the built-in aligner: centre-star multiple alignment ----
+@dataclass
+class StarAlignment:
+    """What ldpc_dna_star_align[_host] returns for a batch of groups."""
+    center: np.ndarray     # [G] int32: the centre's index inside its group (-1: empty group)
+    width: np.ndarray      # [G] int32: the aligned width
+    out_ptr: np.ndarray    # [G+1] int64: group g's rows start at out[out_ptr[g]]
+    out: np.ndarray        # uint8: the rows, width[g] bytes each, in input order
+    dist: np.ndarray       # [n_seqs] int32: Levenshtein distance of every read to its group's centre
+    group_ptr: np.ndarray  # [G+1] int64
+    n_host_groups: int = 0  # device form: groups of >= 2 reads aligned by the host code inside the call
+    n_passes: int = 0       # device form: kernel passes (the workspace budget splits the pairs)
+    n_pairs: int = 0        # device form: pairs aligned on the device
+
+    def rows(self, g: int) -> List[bytes]:
+        k = int(self.group_ptr[g + 1] - self.group_ptr[g])
+        w, o = int(self.width[g]), int(self.out_ptr[g])
+        return [self.out[o + r * w:o + (r + 1) * w].tobytes() for r in range(k)]
+
+
+def star_align_batch(groups: Sequence[Sequence[str]], device: int = 0, host: bool = False,
+                     workspace_bytes: int = 0) -> StarAlignment:
+    """The centre-star alignment of every group (each a list of reads) in
+    one call: on the GPU (`device`; workspace_bytes bounds the
+    traceback workspace of one kernel pass, 0 = the library's default), or
+    with host=True on one CPU thread.  The two give identical bytes."""
+    mod, L = _lib()
+    enc = [s for g in groups for s in g]
+    buf, offs, lens = _concat(enc)
+    gp = np.zeros(len(groups) + 1, np.int64)
+    gp[1:] = np.cumsum([len(g) for g in groups], dtype=np.int64)
+    G = len(groups)
+    center, width = np.zeros(max(G, 1), np.int32), np.zeros(max(G, 1), np.int32)
+    out_ptr = np.zeros(G + 1, np.int64)
+    dist = np.zeros(max(len(enc), 1), np.int32)
+    needed, stats = C.c_int64(0), np.zeros(3, np.int64)
+    # a first guess of the output size (twice the longest read per row); the call reports the exact one
+    cap = sum(len(g) * (2 * max((len(s) for s in g), default=0) + 16) for g in groups)
+
+    def call(out):
+        head = (_p(buf), _p(offs), _p(lens), len(enc), _p(gp), G, _p(center), _p(width), _p(out_ptr), _p(out),
+                len(out), C.byref(needed), _p(dist))
+        if host:
+            return L.ldpc_dna_star_align_host(*head)
+        return L.ldpc_dna_star_align(*head, device, int(workspace_bytes), _p(stats))
+
+    out = np.zeros(max(cap, 1), np.uint8)
+    rc = call(out)
+    if rc == mod.LDPC_ERR_ARG and needed.value > len(out):
+        out = np.zeros(needed.value, np.uint8)
+        rc = call(out)
+    mod._check(rc)
+    return StarAlignment(center=center[:G], width=width[:G], out_ptr=out_ptr, out=out[:needed.value],
+                         dist=dist[:len(enc)], group_ptr=gp, n_host_groups=int(stats[0]), n_passes=int(stats[1]),
+                         n_pairs=int(stats[2]))
+
+
+def star_align_groups(groups: Sequence[Sequence[str]], device: int = 0, host: bool = False,
+                      workspace_bytes: int = 0) -> List[List[Tuple[int, str]]]:
+    """star_align for many groups in one call (on GPU `device`, or on the
+    CPU with host=True): per group the AlignFn records [(order, row)]."""
+    res = star_align_batch(groups, device, host, workspace_bytes)
+    return [[(k, r.decode("latin-1")) for k, r in enumerate(res.rows(g))] for g in range(len(groups))]
+
+
+def star_align(seqs: Sequence[str]) -> List[Tuple[int, str]]:
+    """The built-in AlignFn (host only, one group): the deterministic
+    centre-star multiple alignment of DESIGN.md sec. 8.6 -- the centre is the
+    read with the smallest sum of Levenshtein distances to the others, every
+    other read is aligned to it, insertions share '-'-padded columns.
+    Records come back in input order as (order, row)."""
+    return star_align_groups([list(seqs)], host=True)[0]
+
+
 def py_float_repr(v: float) -> str:
     """The library's Python-repr formatter (used by the soft-file writer)."""
     mod, L = _lib()
@@ -247,14 +328,25 @@ class LlrPlan:
     n_reads_valid: int
     n_pairs: int
     n_aligned_strands: int
+    n_align_pairs: int = 0
+    t_align_s: float = 0.0
 
 
 def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int],
              align_fn: Optional[AlignFn] = None, device: int = 0, strands: Optional[np.ndarray] = None,
-             distance_fn=None) -> LlrPlan:
+             distance_fn=None, align_host: Optional[bool] = None) -> LlrPlan:
     """Group and classify the reads (decoder.py:103-497 control flow).
     Pairwise distances of ragged strands come from the GPU
-    (`distance_fn` defaults to edit_distance on `device`)."""
+    (`distance_fn` defaults to edit_distance on `device`).  align_fn is a
+    callable, asked once per ragged strand, or "star": the candidate groups
+    of all ragged strands then go to the built-in aligner in one batched call
+    (star_align_groups on `device`; on the CPU with align_host=True, which is
+    also what a caller gets who keeps the distances off the GPU with a
+    distance_fn and leaves align_host None)."""
+    if isinstance(align_fn, str) and align_fn != "star":
+        raise ValueError(f"unknown aligner {align_fn!r} (a callable or 'star')")
+    if align_host is None:
+        align_host = distance_fn is not None
     distance_fn = distance_fn or (lambda sq, pr: edit_distance(sq, pr, device))
     sidx = strand_indices() if strands is None else np.asarray(strands, np.int64)
     S = len(sidx)
@@ -295,6 +387,8 @@ def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int
     rows_of = {}  # strand -> (row strings, qualities) for aligned / failed strands
     n_pairs = 0
     n_aligned = 0
+    n_align_pairs = 0
+    t_align = 0.0
     if pair_list:
         pairs = np.concatenate(pair_list)
         n_pairs = len(pairs)
@@ -303,6 +397,7 @@ def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int
         d = distance_fn(local, pairs)
         close = d < ED_THRESHOLD
         ps = np.concatenate(pair_strand)
+        todo = []  # (strand, candidates, their qualities) of the strands that go to the aligner
         for s in ragged:
             m = close & (ps == s)
             sel = np.unique(pairs[m].ravel())  # decoder.py:176-178 (np.unique: sorted)
@@ -310,11 +405,18 @@ def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int
                 kind[s] = KIND_NONE  # decoder.py:179-188
                 continue
             if align_fn is None:
-                raise RuntimeError("ragged strands need an aligner (align_fn); MUSCLE is out of scope")
-            cand = [local[i] for i in sel]
-            cq = q_all[read_ids[sel]]
+                raise RuntimeError("ragged strands need an aligner (align_fn='star' or a callable)")
+            todo.append((s, [local[i] for i in sel], q_all[read_ids[sel]]))
+        t0 = time.perf_counter()
+        if align_fn == "star":  # one batched call for all strands
+            records = star_align_groups([cand for _, cand, _ in todo], device=device, host=align_host) if todo else []
+            n_align_pairs = sum(len(cand) - 1 for _, cand, _ in todo)
+        else:
+            records = [align_fn(cand) for _, cand, _ in todo]
+        t_align = time.perf_counter() - t0
+        for (s, cand, cq), recs in zip(todo, records):
             aligned, aq, err, eq = [], [], [], []
-            for order, a in align_fn(cand):  # decoder.py:195-214
+            for order, a in recs:  # decoder.py:195-214
                 if len(a) != PAYLOAD_NT:
                     err.append(a[-1] if a else "")
                     eq.append(int(cq[order]))
@@ -367,7 +469,7 @@ def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int
             row_q[row_ptr[s] + k] = q
 
     return LlrPlan(kind=kind, row_ptr=row_ptr, rows=rows, row_q=row_q, n_reads_valid=len(read_ids),
-                   n_pairs=n_pairs, n_aligned_strands=n_aligned)
+                   n_pairs=n_pairs, n_aligned_strands=n_aligned, n_align_pairs=n_align_pairs, t_align_s=t_align)
 
 
 def build_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int], eps: float = 0.02,
@@ -375,7 +477,8 @@ def build_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[in
               strands: Optional[np.ndarray] = None) -> LlrResult:
     """Reads (decoded index value, payload sequence, quality) -> LlrResult.
     `strands` defaults to strand_indices(); align_fn answers the MUSCLE call
-    for ragged strands (required only if such strands have close pairs)."""
+    for ragged strands (required only if such strands have close pairs):
+    "star" is the built-in aligner on `device`, a callable is asked per strand."""
     mod, L = _lib()
     plan = plan_llr(index_vals, seqs, quals, align_fn, device, strands)
     S = len(plan.kind)
@@ -388,4 +491,5 @@ def build_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[in
                                     unit, _p(llr), _p(mask), _p(codes), C.byref(exact), device))
     return LlrResult(llr=llr, int_mask=mask, kind=plan.kind, n_reads_valid=plan.n_reads_valid,
                      n_pairs=plan.n_pairs, n_aligned_strands=plan.n_aligned_strands,
-                     erased=np.nonzero(plan.kind == KIND_NONE)[0], codes=codes if exact.value else None, unit=unit)
+                     erased=np.nonzero(plan.kind == KIND_NONE)[0], codes=codes if exact.value else None, unit=unit,
+                     n_align_pairs=plan.n_align_pairs, t_align_s=plan.t_align_s)

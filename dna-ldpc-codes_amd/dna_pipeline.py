@@ -127,7 +127,9 @@ def trial_from_reads(reads, codewords: np.ndarray, eps: float = 0.02, max_iter: 
                      decode_fn: Optional[DecodeFn] = None, faithful: bool = True, device: int = 0) -> Dict:
     """decoder.py:120-664 for one trial: reads (index values, payloads,
     qualities) -> LLRs on the GPU (dna_llr.build_llr) -> first and second
-    decode.  Adds the LLR stage's time and strand statistics to the result."""
+    decode.  align_fn: "star" (the built-in aligner, on the GPU) or a
+    callable.  Adds the LLR stage's time and strand statistics to the result,
+    the aligner's share among them (n_align_pairs, t_align_s)."""
     import dna_llr
     t0 = time.perf_counter()
     built = dna_llr.build_llr(*reads, eps=eps, align_fn=align_fn, device=device)
@@ -135,7 +137,7 @@ def trial_from_reads(reads, codewords: np.ndarray, eps: float = 0.02, max_iter: 
     res = decode_trial(built.llr, codewords, eps=eps, max_iter=max_iter, decode_fn=decode_fn, faithful=faithful,
                        codes=built.codes)
     res.update(t_llr_s=t_llr, n_erased_strands=int(len(built.erased)), n_reads_valid=built.n_reads_valid,
-               llr=built)
+               n_align_pairs=built.n_align_pairs, t_align_s=built.t_align_s, llr=built)
     return res
 
 

@@ -139,7 +139,7 @@ EXPORTS = [
     "ldpc_encoder_create", "ldpc_encoder_free", "ldpc_encoder_info", "ldpc_encode_host", "ldpc_encode",
     "ldpc_encoder_encode_device",
     "ldpc_dna_index_encode", "ldpc_dna_index_decode_host", "ldpc_dna_index_decode", "ldpc_dna_strands_host",
-    "ldpc_dna_strands",
+    "ldpc_dna_strands", "ldpc_dna_star_align_host", "ldpc_dna_star_align",
 ]
 
 

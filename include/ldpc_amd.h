@@ -445,6 +445,48 @@ int ldpc_dna_strands_host(const uint8_t *codewords, int32_t n_cw, int64_t N, con
 int ldpc_dna_strands(const uint8_t *codewords, int32_t n_cw, int64_t N, const int32_t *index, uint8_t *out,
                      int32_t device);
 
+/* The aligner of ragged strands (the reference calls
+ * MUSCLE, decoder.py:201-207): a deterministic centre-star multiple alignment
+ * of every group of reads.  Sequence i is seqs[offsets[i] ..
+ * offsets[i]+lengths[i]) (any bytes, any length); group g is sequences
+ * group_ptr[g] .. group_ptr[g+1] (group_ptr[0] = 0, group_ptr[n_groups] =
+ * n_seqs, at most 32768 reads per group).  Per group: the centre is the read
+ * with the smallest sum of Levenshtein distances to the others (ties: lowest
+ * index); every other read is aligned to it by the Levenshtein traceback that
+ * prefers diagonal, then up (an insertion before the centre position), then
+ * left (a '-' on the centre position); insertions of all rows share
+ * left-justified, '-'-padded columns.
+ *
+ * Outputs: center[g] (index inside the group, -1 for an empty group),
+ * width[g], out_ptr[n_groups+1] and the rows: row r of group g is the
+ * width[g] bytes at out + out_ptr[g] + r * width[g], rows in input order.
+ * *out_needed (may be NULL) gets out_ptr[n_groups], the bytes all rows take;
+ * if out_capacity is smaller the call returns LDPC_ERR_ARG with center, width,
+ * out_ptr, *out_needed and dist filled and no row written (out may be NULL
+ * with out_capacity 0: the size query).  dist (may be NULL) gets, per
+ * sequence, its Levenshtein distance to its group's centre.
+ *
+ * The _host form runs on one CPU thread.  ldpc_dna_star_align computes the
+ * in-group distances and the pairwise tables and tracebacks on `device` and
+ * merges on the host; the results are byte-identical.  workspace_bytes bounds
+ * the device memory that holds the traceback moves of one kernel pass (0: 256
+ * MiB); the pairs run in as many passes as that takes.  A group with a read
+ * longer than 800 bytes, or with a pair whose moves (64 * m * ceil(n / 16) * 4
+ * bytes for a read of m and a centre of n bytes) exceed workspace_bytes, is
+ * aligned by the host code inside the call.  stats (may be NULL) gets
+ * {groups of two or more reads aligned on the host, kernel passes, pairs
+ * aligned on the device}.  Null pointers, negative counts, a group_ptr that is
+ * not monotone from 0 to n_seqs, negative or overflowing offsets / lengths and
+ * output sizes that overflow are LDPC_ERR_ARG, checked before any device call. */
+int ldpc_dna_star_align_host(const uint8_t *seqs, const int64_t *offsets, const int32_t *lengths, int64_t n_seqs,
+                             const int64_t *group_ptr, int64_t n_groups, int32_t *center, int32_t *width,
+                             int64_t *out_ptr, uint8_t *out, int64_t out_capacity, int64_t *out_needed,
+                             int32_t *dist);
+int ldpc_dna_star_align(const uint8_t *seqs, const int64_t *offsets, const int32_t *lengths, int64_t n_seqs,
+                        const int64_t *group_ptr, int64_t n_groups, int32_t *center, int32_t *width,
+                        int64_t *out_ptr, uint8_t *out, int64_t out_capacity, int64_t *out_needed, int32_t *dist,
+                        int32_t device, int64_t workspace_bytes, int64_t *stats);
+
 /* Write soft<rs>_n18432_m1860_<i+1>.txt, i < n_files, into dir: row i of
  * llr as str(value)+' ' tokens (decoder.py:511-516, def_func.py:54-57);
  * int_mask (may be NULL) marks the int-0 entries.  Host only. */
