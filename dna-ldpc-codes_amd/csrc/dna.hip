@@ -6,7 +6,9 @@
 //
 // Reference: ex_decoder/decoder.py:142-519 (the strand loop; count rule
 // :266-320 and :442-497), def_func.py:10-26 (edit_dist), :97-117
-// (DNA2binary).  The host mirror (dna_llr.py) classifies every strand into a
+// (DNA2binary).  The planner (dna_llr.plan_llr in Python; in the library
+// dna_plan.hpp on the host and dna_plan_kernels.hpp on the GPU, included at
+// the end of this file) classifies every strand into a
 // `kind` and lays the candidates out as fixed-width rows; these kernels do
 // the arithmetic:
 //
@@ -39,6 +41,7 @@
 
 #include "../../include/ldpc_amd.h"
 #include "engine.hpp"
+#include "dna_plan.hpp"
 #include "rs_index.hpp"
 #include "star_align.hpp"
 
@@ -329,6 +332,31 @@ int dev_copy_in(DevBuf& d, const void* src, size_t bytes)
     return LDPC_OK;
 }
 
+// k_edit_distance on device-resident buffers (the host-buffer entry point, the
+// aligner's centres and the read planner): d_dist[p] for pairs whose indices
+// the caller has checked, lengths <= max_len <= 800.
+int launch_edit_distance(const uint8_t* d_seqs, const int64_t* d_off, const int32_t* d_len, const int32_t* d_pa,
+                         const int32_t* d_pb, int64_t n_pairs, int32_t max_len, int32_t* d_dist)
+{
+    const size_t lds = (sizeof(uint16_t) * (size_t)(max_len + 1) + (size_t)max_len) * 64;
+    hipLaunchKernelGGL(k_edit_distance, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), lds, 0, d_seqs, d_off, d_len,
+                       d_pa, d_pb, n_pairs, max_len, d_dist);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
+// k_dna_llr on a device-resident plan; d_mask, d_codes / d_overflow may be null.
+int launch_dna_llr(const int32_t* d_kind, const int64_t* d_row_ptr, const uint8_t* d_rows, const int32_t* d_row_q,
+                   int32_t n_strands, int32_t payload_nt, double llr_unit, double* d_llr, uint8_t* d_mask,
+                   int8_t* d_codes, int32_t* d_overflow)
+{
+    dim3 grid((unsigned)((n_strands + 255) / 256), (unsigned)payload_nt);
+    hipLaunchKernelGGL(k_dna_llr, grid, dim3(256), 0, 0, d_kind, d_row_ptr, d_rows, d_row_q, n_strands, payload_nt,
+                       llr_unit, d_llr, d_mask, d_codes, d_overflow);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+
 }  // namespace
 }  // namespace ldpc
 
@@ -377,12 +405,10 @@ static int dna_llr(int32_t n_strands, const int32_t* kind, const int64_t* row_pt
         LDPC_HIP(hipMalloc(&dc.p, out_n));
         if ((rc = dev_copy_in(dov, &zero, sizeof zero))) return rc;
     }
-    dim3 grid((unsigned)((n_strands + 255) / 256), (unsigned)payload_nt);
-    hipLaunchKernelGGL(k_dna_llr, grid, dim3(256), 0, 0, dk.as<int32_t>(), dp.as<int64_t>(), dr.as<uint8_t>(),
-                       dq.as<int32_t>(), n_strands, payload_nt, llr_unit, dl.as<double>(),
-                       int_mask ? dm.as<uint8_t>() : nullptr, codes ? dc.as<int8_t>() : nullptr,
-                       codes ? dov.as<int32_t>() : nullptr);
-    LDPC_HIP(hipGetLastError());
+    if ((rc = launch_dna_llr(dk.as<int32_t>(), dp.as<int64_t>(), dr.as<uint8_t>(), dq.as<int32_t>(), n_strands,
+                             payload_nt, llr_unit, dl.as<double>(), int_mask ? dm.as<uint8_t>() : nullptr,
+                             codes ? dc.as<int8_t>() : nullptr, codes ? dov.as<int32_t>() : nullptr)))
+        return rc;
     LDPC_HIP(hipMemcpy(llr, dl.p, sizeof(double) * out_n, hipMemcpyDeviceToHost));
     if (int_mask) LDPC_HIP(hipMemcpy(int_mask, dm.p, out_n, hipMemcpyDeviceToHost));
     if (codes) {
@@ -463,11 +489,9 @@ int ldpc_dna_edit_distance(const uint8_t* seqs, const int64_t* offsets, const in
     if ((rc = dev_copy_in(da, pair_a, sizeof(int32_t) * (size_t)n_pairs))) return rc;
     if ((rc = dev_copy_in(db, pair_b, sizeof(int32_t) * (size_t)n_pairs))) return rc;
     LDPC_HIP(hipMalloc(&dd.p, sizeof(int32_t) * (size_t)n_pairs));
-    const size_t lds = (sizeof(uint16_t) * (size_t)(max_len + 1) + (size_t)max_len) * 64;
-    const unsigned blocks = (unsigned)((n_pairs + 63) / 64);
-    hipLaunchKernelGGL(k_edit_distance, dim3(blocks), dim3(64), lds, 0, ds.as<uint8_t>(), doff.as<int64_t>(),
-                       dlen.as<int32_t>(), da.as<int32_t>(), db.as<int32_t>(), n_pairs, max_len, dd.as<int32_t>());
-    LDPC_HIP(hipGetLastError());
+    if ((rc = launch_edit_distance(ds.as<uint8_t>(), doff.as<int64_t>(), dlen.as<int32_t>(), da.as<int32_t>(),
+                                   db.as<int32_t>(), n_pairs, max_len, dd.as<int32_t>())))
+        return rc;
     LDPC_HIP(hipMemcpy(dist, dd.p, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost));
     return LDPC_OK;
 }
@@ -653,6 +677,7 @@ struct StarCall {
     int64_t out_capacity;
     int64_t* out_needed;
     int32_t* dist;
+    std::vector<uint8_t>* out_vec = nullptr;  // internal callers: sized to the rows and filled instead of out
 };
 
 // What both entry points gather before the merge: the centre of every group
@@ -745,7 +770,11 @@ int star_finish(const std::string& who, const StarCall& a, const StarScripts& s)
     if (a.n_groups > 0) a.out_ptr[a.n_groups] = total;
     if (a.out_needed) *a.out_needed = total;
     if (a.dist) std::copy(s.dist.begin(), s.dist.end(), a.dist);
-    if (total > a.out_capacity) {
+    uint8_t* out = a.out;
+    if (a.out_vec) {
+        a.out_vec->resize((size_t)total);
+        out = a.out_vec->data();
+    } else if (total > a.out_capacity) {
         set_error(who + ": the output buffer holds " + std::to_string(a.out_capacity) + " bytes, the rows need " +
                   std::to_string(total));
         return LDPC_ERR_ARG;
@@ -755,7 +784,7 @@ int star_finish(const std::string& who, const StarCall& a, const StarScripts& s)
         if (k == 0) continue;
         const int64_t c = s.centre[(size_t)g], n = a.lengths[g0 + c];
         const int64_t wd = star::merge_width(s.rows.data() + g0, k, c, n, &w);
-        star::merge_rows(s.rows.data() + g0, k, c, star_seq(a, g0 + c), n, w, wd, a.out + a.out_ptr[g]);
+        star::merge_rows(s.rows.data() + g0, k, c, star_seq(a, g0 + c), n, w, wd, out + a.out_ptr[g]);
     }
     return LDPC_OK;
 }
@@ -781,10 +810,11 @@ int star_align_host(const StarCall& a)
 // Workspace words of one lane-interleaved block: rows x words per row x 64 lanes.
 int64_t star_block_words(int64_t m, int64_t wpr) { return m * wpr * 64; }
 
-int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes, int64_t* stats)
+// dev_seqs (may be null): a.seqs already resident on `device` (the read planner's reads).
+int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes, int64_t* stats,
+                      const std::string& who = "ldpc_dna_star_align", const uint8_t* dev_seqs = nullptr)
 {
     using namespace ldpc;
-    const std::string who = "ldpc_dna_star_align";
     if (stats) stats[0] = stats[1] = stats[2] = 0;
     if (int rc = star_args(who, a)) return rc;
     if (workspace_bytes < 0) {
@@ -824,7 +854,8 @@ int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes
     }
     DevBuf ds, doff, dlen;
     int rc;
-    if ((rc = dev_copy_in(ds, a.seqs, (size_t)seq_bytes))) return rc;
+    if (!dev_seqs && (rc = dev_copy_in(ds, a.seqs, (size_t)seq_bytes))) return rc;
+    const uint8_t* d_seqs = dev_seqs ? dev_seqs : ds.as<uint8_t>();
     if ((rc = dev_copy_in(doff, a.offsets, sizeof(int64_t) * (size_t)a.n_seqs))) return rc;
     if ((rc = dev_copy_in(dlen, a.lengths, sizeof(int32_t) * (size_t)a.n_seqs))) return rc;
 
@@ -845,11 +876,9 @@ int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes
         if ((rc = dev_copy_in(da, pa.data(), sizeof(int32_t) * (size_t)np))) return rc;
         if ((rc = dev_copy_in(db, pb.data(), sizeof(int32_t) * (size_t)np))) return rc;
         LDPC_HIP(hipMalloc(&dd.p, sizeof(int32_t) * (size_t)np));
-        const size_t lds = (sizeof(uint16_t) * (size_t)(max_len + 1) + (size_t)max_len) * 64;
-        hipLaunchKernelGGL(k_edit_distance, dim3((unsigned)((np + 63) / 64)), dim3(64), lds, 0, ds.as<uint8_t>(),
-                           doff.as<int64_t>(), dlen.as<int32_t>(), da.as<int32_t>(), db.as<int32_t>(), np, max_len,
-                           dd.as<int32_t>());
-        LDPC_HIP(hipGetLastError());
+        if ((rc = launch_edit_distance(d_seqs, doff.as<int64_t>(), dlen.as<int32_t>(), da.as<int32_t>(),
+                                       db.as<int32_t>(), np, max_len, dd.as<int32_t>())))
+            return rc;
         LDPC_HIP(hipMemcpy(d.data(), dd.p, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost));
         np = 0;
         std::vector<int64_t> dm;
@@ -949,7 +978,7 @@ int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes
         const size_t lds = (sizeof(uint16_t) * (size_t)(max_n + 1) + (size_t)max_n) * 64;
         for (int64_t q = 0; q < passes; q++) {
             const int64_t b0 = pass_first[(size_t)q], nb = pass_first[(size_t)q + 1] - b0;
-            hipLaunchKernelGGL(k_star_align_pairs, dim3((unsigned)nb), dim3(64), lds, 0, ds.as<uint8_t>(),
+            hipLaunchKernelGGL(k_star_align_pairs, dim3((unsigned)nb), dim3(64), lds, 0, d_seqs,
                                doff.as<int64_t>(), dlen.as<int32_t>(), dpr.as<int32_t>(), dpc.as<int32_t>(),
                                dbf.as<int64_t>(), dbw.as<int64_t>(), dbp.as<int32_t>(), dao.as<int64_t>(),
                                dio.as<int64_t>(), b0, max_n, dws.as<uint32_t>(), dat.as<uint8_t>(), dcnt.as<int32_t>(),
@@ -1016,6 +1045,116 @@ int ldpc_dna_star_align(const uint8_t* seqs, const int64_t* offsets, const int32
         return star_align_device(a, device, workspace_bytes, stats);
     } catch (const std::bad_alloc&) {
         set_error("ldpc_dna_star_align: out of host memory");
+        return LDPC_ERR_DEVICE;
+    }
+}
+
+}  // extern "C"
+
+// --- the read planner (dna_plan.hpp) --------------------
+#include "dna_plan_kernels.hpp"
+
+namespace {
+
+ldpc::plan::Args plan_args(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, const int32_t* quals,
+                           int64_t n_reads, const int32_t* index_vals, const int32_t* strands, int32_t n_strands,
+                           int32_t payload_nt, int32_t align, int32_t* kind, int64_t* row_ptr, uint8_t* rows,
+                           int32_t* row_q, int64_t* stats)
+{
+    return ldpc::plan::Args{seqs, offsets, lengths, quals, n_reads, index_vals, strands, n_strands,
+                            payload_nt, align, kind, row_ptr, rows, row_q, stats};
+}
+
+int reads_llr(const ldpc::plan::Args& a, int32_t device, int64_t workspace_bytes, double llr_unit, double* llr,
+              uint8_t* int_mask, int8_t* codes, int32_t* codes_exact)
+{
+    using namespace ldpc;
+    const std::string who = "ldpc_dna_reads_llr";
+    if (!llr || (codes && !codes_exact)) {
+        set_error(who + ": bad arguments");
+        return LDPC_ERR_ARG;
+    }
+    PlanDev pd;
+    if (int rc = plan_device(who, a, false, device, workspace_bytes, &pd)) return rc;
+    if (codes_exact) *codes_exact = 1;
+    if (a.n_strands == 0) return LDPC_OK;
+    const size_t out_n = (size_t)2 * a.payload_nt * a.n_strands;
+    DevBuf dl, dm, dc, dov;
+    int rc;
+    LDPC_HIP(hipMalloc(&dl.p, sizeof(double) * out_n));
+    if (int_mask) LDPC_HIP(hipMalloc(&dm.p, out_n));
+    if (codes) {
+        const int32_t zero = 0;
+        LDPC_HIP(hipMalloc(&dc.p, out_n));
+        if ((rc = dev_copy_in(dov, &zero, sizeof zero))) return rc;
+    }
+    if ((rc = launch_dna_llr(pd.kind.as<int32_t>(), pd.row_ptr.as<int64_t>(), pd.rows.as<uint8_t>(),
+                             pd.row_q.as<int32_t>(), a.n_strands, a.payload_nt, llr_unit, dl.as<double>(),
+                             int_mask ? dm.as<uint8_t>() : nullptr, codes ? dc.as<int8_t>() : nullptr,
+                             codes ? dov.as<int32_t>() : nullptr)))
+        return rc;
+    LDPC_HIP(hipMemcpy(llr, dl.p, sizeof(double) * out_n, hipMemcpyDeviceToHost));
+    if (int_mask) LDPC_HIP(hipMemcpy(int_mask, dm.p, out_n, hipMemcpyDeviceToHost));
+    if (codes) {
+        int32_t ov = 0;
+        LDPC_HIP(hipMemcpy(codes, dc.p, out_n, hipMemcpyDeviceToHost));
+        LDPC_HIP(hipMemcpy(&ov, dov.p, sizeof ov, hipMemcpyDeviceToHost));
+        *codes_exact = ov ? 0 : 1;
+    }
+    return LDPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_dna_plan_host(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, const int32_t* quals,
+                       int64_t n_reads, const int32_t* index_vals, const int32_t* strands, int32_t n_strands,
+                       int32_t payload_nt, int32_t align, int32_t* kind, int64_t* row_ptr, uint8_t* rows,
+                       int32_t* row_q, int64_t* stats)
+{
+    try {
+        const std::string err = ldpc::plan::plan_host(plan_args(seqs, offsets, lengths, quals, n_reads, index_vals,
+                                                                strands, n_strands, payload_nt, align, kind, row_ptr,
+                                                                rows, row_q, stats));
+        if (err.empty()) return LDPC_OK;
+        set_error("ldpc_dna_plan_host: " + err);
+        return LDPC_ERR_ARG;
+    } catch (const std::bad_alloc&) {
+        set_error("ldpc_dna_plan_host: out of host memory");
+        return LDPC_ERR_DEVICE;
+    }
+}
+
+int ldpc_dna_plan(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, const int32_t* quals,
+                  int64_t n_reads, const int32_t* index_vals, const int32_t* strands, int32_t n_strands,
+                  int32_t payload_nt, int32_t align, int32_t device, int64_t workspace_bytes, int32_t* kind,
+                  int64_t* row_ptr, uint8_t* rows, int32_t* row_q, int64_t* stats)
+{
+    try {
+        ldpc::PlanDev pd;
+        return ldpc::plan_device("ldpc_dna_plan", plan_args(seqs, offsets, lengths, quals, n_reads, index_vals, strands,
+                                                            n_strands, payload_nt, align, kind, row_ptr, rows, row_q,
+                                                            stats),
+                                 true, device, workspace_bytes, &pd);
+    } catch (const std::bad_alloc&) {
+        set_error("ldpc_dna_plan: out of host memory");
+        return LDPC_ERR_DEVICE;
+    }
+}
+
+int ldpc_dna_reads_llr(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, const int32_t* quals,
+                       int64_t n_reads, const int32_t* index_vals, const int32_t* strands, int32_t n_strands,
+                       int32_t payload_nt, int32_t align, int32_t device, int64_t workspace_bytes, double llr_unit,
+                       double* llr, uint8_t* int_mask, int8_t* codes, int32_t* codes_exact, int32_t* kind,
+                       int64_t* stats)
+{
+    try {
+        return reads_llr(plan_args(seqs, offsets, lengths, quals, n_reads, index_vals, strands, n_strands, payload_nt,
+                                   align, kind, nullptr, nullptr, nullptr, stats),
+                         device, workspace_bytes, llr_unit, llr, int_mask, codes, codes_exact);
+    } catch (const std::bad_alloc&) {
+        set_error("ldpc_dna_reads_llr: out of host memory");
         return LDPC_ERR_DEVICE;
     }
 }

@@ -32,6 +32,12 @@ older parity tests hand the same deterministic `pad_align` stand-in to the
 product and to the oracle) or the built-in centre-star alignment,
 align_fn="star" (star_align / star_align_groups), whose
 pairwise tables and tracebacks run on the GPU.
+
+Steps 0-2 also exist in the library: plan_llr_native,
+build_llr(native=True) and ldpc_dna_reads_llr run the grouping,
+classification, pair enumeration, candidate selection and row layout as GPU
+kernels (csrc/dna_plan_kernels.hpp) or on one CPU thread (csrc/dna_plan.hpp),
+with plan_llr below as their yardstick.
 """
 from __future__ import annotations
 
@@ -49,6 +55,8 @@ N_STRANDS = 18432         # decoder.py:509 (range(18432))
 ED_THRESHOLD = 15         # decoder.py:175 (temp < 15)
 
 KIND_NONE, KIND_COUNT, KIND_SHORT, KIND_ALIGN_FAILED = 0, 1, 2, 3
+
+_NO_ALIGNER = "ragged strands need an aligner (align_fn='star' or a callable)"
 
 AlignFn = Callable[[List[str]], List[Tuple[int, str]]]
 
@@ -131,6 +139,10 @@ def _lib():
         L.ldpc_dna_strands.argtypes = [vp, i32, i64, vp, vp, i32]
         L.ldpc_dna_star_align_host.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp]
         L.ldpc_dna_star_align.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i32, i64, vp]
+        L.ldpc_dna_plan_host.argtypes = [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.ldpc_dna_plan.argtypes = [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp]
+        L.ldpc_dna_reads_llr.argtypes = [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i64, C.c_double, vp, vp,
+                                         vp, vp, vp, vp]
         L._dna_bound = True
     return ldpc_amd, L
 
@@ -158,8 +170,9 @@ def edit_distance(seqs: Sequence[str], pairs: np.ndarray, device: int = 0) -> np
     return out
 
 
-def _concat(seqs: Sequence[str]):
-    """Sequences as the C ABI takes them: concatenated bytes, offsets, lengths."""
+def _concat(seqs):
+    """Sequences as the C ABI takes them: concatenated bytes, offsets, lengths
+    (the packed triple the native planner also accepts in place of a list)."""
     enc = [s.encode("latin-1", "replace") for s in seqs]
     lens = np.array([len(b) for b in enc], np.int32)
     offs = np.zeros(len(enc), np.int64)
@@ -330,6 +343,7 @@ class LlrPlan:
     n_aligned_strands: int
     n_align_pairs: int = 0
     t_align_s: float = 0.0
+    cnumerr_hist: dict = field(default_factory=dict)        # plan_llr_native on raw reads
 
 
 def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int],
@@ -405,7 +419,7 @@ def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int
                 kind[s] = KIND_NONE  # decoder.py:179-188
                 continue
             if align_fn is None:
-                raise RuntimeError("ragged strands need an aligner (align_fn='star' or a callable)")
+                raise RuntimeError(_NO_ALIGNER)
             todo.append((s, [local[i] for i in sel], q_all[read_ids[sel]]))
         t0 = time.perf_counter()
         if align_fn == "star":  # one batched call for all strands
@@ -472,13 +486,121 @@ def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int
                    n_pairs=n_pairs, n_aligned_strands=n_aligned, n_align_pairs=n_align_pairs, t_align_s=t_align)
 
 
+# --- the native planner (csrc/dna_plan.hpp) -------------
+N_PLAN_STATS = 9  # include/ldpc_amd.h: valid, pairs, aligned strands, alignments, R, cnumerr -1 / 0 / 1 / 2
+
+
+def _packed(seqs):
+    """(buf, offsets, lengths) of a list of str, or the triple itself."""
+    if isinstance(seqs, tuple) and len(seqs) == 3 and isinstance(seqs[0], np.ndarray):
+        buf, offs, lens = seqs
+        return (np.ascontiguousarray(buf, np.uint8), np.ascontiguousarray(offs, np.int64),
+                np.ascontiguousarray(lens, np.int32))
+    return _concat(seqs)
+
+
+def _native_inputs(index_vals, seqs, quals, strands):
+    buf, offs, lens = _packed(seqs)
+    n = len(lens)
+    q = np.ascontiguousarray(quals, np.int32).reshape(-1)
+    iv = None
+    if index_vals is not None:
+        iv64 = np.asarray(index_vals, np.int64).reshape(-1)
+        # an index outside int32 is no strand index (strand values are checked below): any invalid value will do
+        iv = np.ascontiguousarray(np.where((iv64 < -(1 << 31)) | (iv64 >= (1 << 31)), -1, iv64), np.int32)
+    if len(q) != n or (iv is not None and len(iv) != n):
+        raise ValueError("index_vals, seqs and quals must have the same length")
+    sidx64 = strand_indices() if strands is None else np.asarray(strands, np.int64).reshape(-1)
+    if sidx64.size and (sidx64.min() < -(1 << 31) or sidx64.max() >= (1 << 31)):
+        raise ValueError("strand index values must fit int32")
+    return buf, offs, lens, q, iv, np.ascontiguousarray(sidx64, np.int32), n
+
+
+def _native_check(mod, rc):
+    """The library's error as plan_llr raises it."""
+    if rc == mod.LDPC_ERR_ARG:
+        msg = mod.lib().ldpc_last_error().decode()
+        if "need an aligner" in msg:
+            raise RuntimeError(_NO_ALIGNER)
+        if "empty read on strand" in msg:
+            raise ValueError(msg.split(": ", 1)[-1])
+    mod._check(rc)
+
+
+def plan_llr_native(index_vals, seqs, quals, device: int = 0, host: bool = False,
+                    strands: Optional[np.ndarray] = None, align: bool = True, workspace_bytes: int = 0) -> LlrPlan:
+    """plan_llr(..., align_fn="star") in the library: ldpc_dna_plan on GPU
+    `device`, or ldpc_dna_plan_host on one CPU thread (host=True); the same
+    bytes either way.  index_vals None: `seqs` are raw reads, whose 16-nt
+    prefix is decoded and dropped inside the call (split_reads).  seqs is a
+    list of str or an already packed (buf, offsets, lengths) triple (_concat).
+    align=False is align_fn=None.  The cnumerr histogram of raw reads is
+    plan.cnumerr_hist."""
+    mod, L = _lib()
+    buf, offs, lens, q, iv, sidx, n = _native_inputs(index_vals, seqs, quals, strands)
+    S = len(sidx)
+    kind = np.zeros(S, np.int32)
+    row_ptr = np.zeros(S + 1, np.int64)
+    rows = np.full((max(n, 1), PAYLOAD_NT), ord("-"), np.uint8)
+    row_q = np.zeros(max(n, 1), np.int32)
+    stats = np.zeros(N_PLAN_STATS, np.int64)
+    head = (_p(buf), _p(offs), _p(lens), _p(q), n, None if iv is None else _p(iv), _p(sidx), S, PAYLOAD_NT,
+            1 if align else 0)
+    tail = (_p(kind), _p(row_ptr), _p(rows), _p(row_q), _p(stats))
+    if host:
+        rc = L.ldpc_dna_plan_host(*head, *tail)
+    else:
+        rc = L.ldpc_dna_plan(*head, device, int(workspace_bytes), *tail)
+    _native_check(mod, rc)
+    R = int(row_ptr[-1])
+    plan = LlrPlan(kind=kind, row_ptr=row_ptr, rows=rows[:max(R, 1)], row_q=row_q[:max(R, 1)],
+                   n_reads_valid=int(stats[0]), n_pairs=int(stats[1]), n_aligned_strands=int(stats[2]),
+                   n_align_pairs=int(stats[3]), t_align_s=0.0)
+    plan.cnumerr_hist = {k: int(stats[6 + k]) for k in (-1, 0, 1, 2)}
+    return plan
+
+
+def _native_align(align_fn) -> bool:
+    if align_fn is not None and align_fn != "star":
+        raise ValueError("native=True takes align_fn None or 'star' (callable aligners run in the Python planner)")
+    return align_fn == "star"
+
+
+def build_llr_native(index_vals, seqs, quals, eps: float = 0.02, align: bool = True, device: int = 0,
+                     strands: Optional[np.ndarray] = None, workspace_bytes: int = 0):
+    """ldpc_dna_reads_llr: reads (raw when index_vals is None; a list of str or
+    a packed triple) -> (LlrResult, cnumerr histogram) in one library call."""
+    mod, L = _lib()
+    buf, offs, lens, q, iv, sidx, n = _native_inputs(index_vals, seqs, quals, strands)
+    S = len(sidx)
+    unit = math.log((1 - eps) / eps)  # decoder.py:297
+    llr = np.zeros((2 * PAYLOAD_NT, S), np.float64)
+    mask = np.zeros((2 * PAYLOAD_NT, S), np.uint8)
+    codes = np.zeros((2 * PAYLOAD_NT, S), np.int8)
+    kind = np.zeros(S, np.int32)
+    stats = np.zeros(N_PLAN_STATS, np.int64)
+    exact = C.c_int32(0)
+    _native_check(mod, L.ldpc_dna_reads_llr(_p(buf), _p(offs), _p(lens), _p(q), n, None if iv is None else _p(iv),
+                                            _p(sidx), S, PAYLOAD_NT, 1 if align else 0, device, int(workspace_bytes),
+                                            unit, _p(llr), _p(mask), _p(codes), C.byref(exact), _p(kind), _p(stats)))
+    res = LlrResult(llr=llr, int_mask=mask, kind=kind, n_reads_valid=int(stats[0]), n_pairs=int(stats[1]),
+                    n_aligned_strands=int(stats[2]), erased=np.nonzero(kind == KIND_NONE)[0],
+                    codes=codes if exact.value else None, unit=unit, n_align_pairs=int(stats[3]), t_align_s=0.0)
+    return res, {k: int(stats[6 + k]) for k in (-1, 0, 1, 2)}
+
+
 def build_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int], eps: float = 0.02,
               align_fn: Optional[AlignFn] = None, device: int = 0,
-              strands: Optional[np.ndarray] = None) -> LlrResult:
+              strands: Optional[np.ndarray] = None, native: bool = False) -> LlrResult:
     """Reads (decoded index value, payload sequence, quality) -> LlrResult.
     `strands` defaults to strand_indices(); align_fn answers the MUSCLE call
     for ragged strands (required only if such strands have close pairs):
-    "star" is the built-in aligner on `device`, a callable is asked per strand."""
+    "star" is the built-in aligner on `device`, a callable is asked per strand.
+    native=True: the planner runs in the library too (ldpc_dna_reads_llr, one
+    call; align_fn None or "star"; seqs may be a packed triple; t_align_s is
+    not measured and reads 0.0)."""
+    if native:
+        return build_llr_native(index_vals, seqs, quals, eps, _native_align(align_fn), device, strands)[0]
     mod, L = _lib()
     plan = plan_llr(index_vals, seqs, quals, align_fn, device, strands)
     S = len(plan.kind)

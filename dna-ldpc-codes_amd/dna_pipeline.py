@@ -123,22 +123,28 @@ def decode_trial(llr: np.ndarray, codewords: np.ndarray, eps: float = 0.02, max_
     }
 
 
-def trial_from_reads(reads, codewords: np.ndarray, eps: float = 0.02, max_iter: int = 200, align_fn=None,
-                     decode_fn: Optional[DecodeFn] = None, faithful: bool = True, device: int = 0) -> Dict:
-    """decoder.py:120-664 for one trial: reads (index values, payloads,
-    qualities) -> LLRs on the GPU (dna_llr.build_llr) -> first and second
-    decode.  align_fn: "star" (the built-in aligner, on the GPU) or a
-    callable.  Adds the LLR stage's time and strand statistics to the result,
-    the aligner's share among them (n_align_pairs, t_align_s)."""
-    import dna_llr
-    t0 = time.perf_counter()
-    built = dna_llr.build_llr(*reads, eps=eps, align_fn=align_fn, device=device)
-    t_llr = time.perf_counter() - t0
+def _finish_trial(built, t_llr, codewords, eps, max_iter, decode_fn, faithful) -> Dict:
     res = decode_trial(built.llr, codewords, eps=eps, max_iter=max_iter, decode_fn=decode_fn, faithful=faithful,
                        codes=built.codes)
     res.update(t_llr_s=t_llr, n_erased_strands=int(len(built.erased)), n_reads_valid=built.n_reads_valid,
                n_align_pairs=built.n_align_pairs, t_align_s=built.t_align_s, llr=built)
     return res
+
+
+def trial_from_reads(reads, codewords: np.ndarray, eps: float = 0.02, max_iter: int = 200, align_fn=None,
+                     decode_fn: Optional[DecodeFn] = None, faithful: bool = True, device: int = 0,
+                     native: bool = False) -> Dict:
+    """decoder.py:120-664 for one trial: reads (index values, payloads,
+    qualities) -> LLRs on the GPU (dna_llr.build_llr) -> first and second
+    decode.  align_fn: "star" (the built-in aligner, on the GPU) or a
+    callable.  Adds the LLR stage's time and strand statistics to the result,
+    the aligner's share among them (n_align_pairs, t_align_s).  native=True:
+    the planner runs in the library as well (build_llr(native=True))."""
+    import dna_llr
+    t0 = time.perf_counter()
+    built = dna_llr.build_llr(*reads, eps=eps, align_fn=align_fn, device=device, native=native)
+    t_llr = time.perf_counter() - t0
+    return _finish_trial(built, t_llr, codewords, eps, max_iter, decode_fn, faithful)
 
 
 def read_trial_files(directory: str, rs: int, trial: int):
@@ -161,12 +167,23 @@ def read_trial_files(directory: str, rs: int, trial: int):
 
 def trial_from_raw_reads(raw_reads, codewords: np.ndarray, eps: float = 0.02, max_iter: int = 200, align_fn=None,
                          decode_fn: Optional[DecodeFn] = None, faithful: bool = True, device: int = 0,
-                         host_index: bool = False) -> Dict:
+                         host_index: bool = False, native: bool = False) -> Dict:
     """decoder.py:59-664 for one trial: raw reads (sequences, qualities) ->
     index decode on the GPU (dna_llr.split_reads; host_index=True: on the CPU)
     -> trial_from_reads.  Adds the index stage's time, the number of reads it
-    dropped and the histogram of cnumerr."""
+    dropped and the histogram of cnumerr.  native=True: the raw reads (a list
+    of str or a packed (buf, offsets, lengths) triple) go straight to
+    ldpc_dna_reads_llr -- index decode, planner and LLRs in one library call, so
+    t_index_s is 0.0 and its time is part of t_llr_s."""
     import dna_llr
+    if native:
+        seqs, quals = raw_reads
+        t0 = time.perf_counter()
+        built, hist = dna_llr.build_llr_native(None, seqs, quals, eps=eps, align=dna_llr._native_align(align_fn),
+                                               device=device)
+        res = _finish_trial(built, time.perf_counter() - t0, codewords, eps, max_iter, decode_fn, faithful)
+        res.update(t_index_s=0.0, n_reads_dropped=hist[-1], cnumerr_hist=hist)
+        return res
     t0 = time.perf_counter()
     reads, hist = dna_llr.split_reads_counted(*raw_reads, device=device, host=host_index)
     t_index = time.perf_counter() - t0

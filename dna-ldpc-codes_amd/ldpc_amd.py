@@ -140,6 +140,7 @@ EXPORTS = [
     "ldpc_encoder_encode_device",
     "ldpc_dna_index_encode", "ldpc_dna_index_decode_host", "ldpc_dna_index_decode", "ldpc_dna_strands_host",
     "ldpc_dna_strands", "ldpc_dna_star_align_host", "ldpc_dna_star_align",
+    "ldpc_dna_plan_host", "ldpc_dna_plan", "ldpc_dna_reads_llr",
 ]
 
 

@@ -381,7 +381,8 @@ int ldpc_encoder_encode_device(const ldpc_encoder *e, int32_t device, void *stre
 /* ------------------------------------------------------------------------ */
 /* Per-strand LLRs from read candidates -- the arithmetic of decoder.py's
  * strand loop (ex_decoder/decoder.py:142-519; count rule :266-320,
- * :442-497).  The caller (dna_llr.py) classifies strand s into kind[s]:
+ * :442-497).  The caller (ldpc_dna_plan below, or dna_llr.py) classifies
+ * strand s into kind[s]:
  *   0 no LLRs, 1 count over its rows, 2 one short candidate, 3 alignment
  *   failed (count of the failed rows' last bases)
  * and lays the candidate rows of strand s at rows[row_ptr[s]..row_ptr[s+1])
@@ -486,6 +487,72 @@ int ldpc_dna_star_align(const uint8_t *seqs, const int64_t *offsets, const int32
                         const int64_t *group_ptr, int64_t n_groups, int32_t *center, int32_t *width,
                         int64_t *out_ptr, uint8_t *out, int64_t out_capacity, int64_t *out_needed, int32_t *dist,
                         int32_t device, int64_t workspace_bytes, int64_t *stats);
+
+/* The read planner (decoder.py:103-497, what
+ * dna_llr.plan_llr does in Python): reads -> the kind / row_ptr / rows / row_q
+ * plan that ldpc_dna_llr consumes.
+ *
+ * Inputs.  Read i is seqs[offsets[i] .. offsets[i]+lengths[i]) with quality
+ * quals[i].  With index_vals[n_reads] a read is its payload and index_vals[i]
+ * its decoded index.  With index_vals = NULL the reads are raw: the first 16
+ * bytes go through the RS(8,4) decoder of ldpc_dna_index_decode, reads with
+ * cnumerr -1 are dropped and the payload is the bytes from 16 on.
+ * strands[n_strands] are the valid index values, strictly ascending; a read
+ * whose index is not among them is dropped, the others are grouped per strand
+ * in input order.  align: 1 = the centre-star aligner of ldpc_dna_star_align,
+ * 0 = no aligner (a ragged strand with candidates is then LDPC_ERR_ARG).
+ *
+ * Per strand: no reads -> kind 0; one read -> kind 2 if shorter than
+ * payload_nt, else 1; several reads all exactly payload_nt long -> kind 1;
+ * otherwise the strand is ragged: the Levenshtein distance of every pair
+ * i < k of its reads is taken, the candidates are the reads with a partner at
+ * distance < 15 (the reference's constant), in input order; none -> kind 0;
+ * otherwise the candidates are aligned as one group: aligned width ==
+ * payload_nt -> kind 1 with the aligned rows, any other width -> kind 3, each
+ * row holding the last byte of its aligned row in byte 0.
+ *
+ * Outputs.  kind[n_strands], row_ptr[n_strands + 1], and R = row_ptr[n_strands]
+ * rows of payload_nt bytes prefilled with '-': a plain kind-1 strand has each
+ * read's first payload_nt bytes, kind 2 the read's last byte in byte 0 ('-'
+ * for an empty read; an empty read with quality > 63 is LDPC_ERR_ARG naming
+ * the strand); row_q[r] is the quality of row r's read.  R <= n_reads, so the
+ * caller allocates rows[max(n_reads, 1)][payload_nt] and row_q[max(n_reads,
+ * 1)]; rows from R on are not touched.  stats (may be NULL), int64[9]:
+ *   [0] reads valid after both filters     [1] distance pairs
+ *   [2] ragged strands sent to the aligner [3] read-to-centre alignments
+ *   [4] R                                  [5..8] reads with cnumerr -1, 0, 1, 2
+ *                                                 (all 0 with index_vals)
+ * Null pointers, negative counts, payload_nt < 1, strands not strictly
+ * ascending and negative or overflowing offsets / lengths are LDPC_ERR_ARG,
+ * checked before any device call; n_reads = 0 gives all kinds 0.
+ *
+ * ldpc_dna_plan_host runs on one CPU thread and has no limit on read length.
+ * ldpc_dna_plan runs the grouping, classification, pair enumeration, distances,
+ * candidate selection and row layout as kernels on `device` and gives the same
+ * bytes; the aligner is ldpc_dna_star_align's (workspace_bytes as there, 0 =
+ * its default), whose merge is host code.  It inherits the distance kernel's
+ * limit: a ragged strand holding a read longer than 800 bytes is LDPC_ERR_ARG
+ * naming the read. */
+int ldpc_dna_plan_host(const uint8_t *seqs, const int64_t *offsets, const int32_t *lengths, const int32_t *quals,
+                       int64_t n_reads, const int32_t *index_vals, const int32_t *strands, int32_t n_strands,
+                       int32_t payload_nt, int32_t align, int32_t *kind, int64_t *row_ptr, uint8_t *rows,
+                       int32_t *row_q, int64_t *stats);
+int ldpc_dna_plan(const uint8_t *seqs, const int64_t *offsets, const int32_t *lengths, const int32_t *quals,
+                  int64_t n_reads, const int32_t *index_vals, const int32_t *strands, int32_t n_strands,
+                  int32_t payload_nt, int32_t align, int32_t device, int64_t workspace_bytes, int32_t *kind,
+                  int64_t *row_ptr, uint8_t *rows, int32_t *row_q, int64_t *stats);
+
+/* Raw reads in, decoder input out: ldpc_dna_plan followed by
+ * ldpc_dna_llr_codes in one call, the plan never leaving the device.  Inputs
+ * as ldpc_dna_plan; outputs as ldpc_dna_llr_codes: llr[2*payload_nt][n_strands],
+ * int_mask (may be NULL), codes with *codes_exact (codes may be NULL), plus
+ * kind[n_strands] (may be NULL) and stats (may be NULL).  The results equal
+ * those of the two calls. */
+int ldpc_dna_reads_llr(const uint8_t *seqs, const int64_t *offsets, const int32_t *lengths, const int32_t *quals,
+                       int64_t n_reads, const int32_t *index_vals, const int32_t *strands, int32_t n_strands,
+                       int32_t payload_nt, int32_t align, int32_t device, int64_t workspace_bytes, double llr_unit,
+                       double *llr, uint8_t *int_mask, int8_t *codes, int32_t *codes_exact, int32_t *kind,
+                       int64_t *stats);
 
 /* Write soft<rs>_n18432_m1860_<i+1>.txt, i < n_files, into dir: row i of
  * llr as str(value)+' ' tokens (decoder.py:511-516, def_func.py:54-57);
