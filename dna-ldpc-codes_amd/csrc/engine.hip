@@ -54,7 +54,8 @@ constexpr int64_t kResAutoMaxTiles = 4;       // explicit pools above this: grou
 constexpr int kProbes = 4;                    // placement probe: candidate scratch allocations timed at init
 
 constexpr int32_t kDefaultFlags = LDPC_SCHED_NONTEMPORAL | LDPC_SCHED_CONTINUOUS | LDPC_SCHED_MSA_COMPRESSED |
-                                  LDPC_SCHED_RESIDENT | LDPC_SCHED_FIRST_FROM_PRIOR | LDPC_SCHED_LR_TABLE;
+                                  LDPC_SCHED_RESIDENT | LDPC_SCHED_FIRST_FROM_PRIOR | LDPC_SCHED_LR_TABLE |
+                                  LDPC_SCHED_HANDOVER;
 constexpr int32_t kAllFlags = kDefaultFlags | LDPC_SCHED_DEBUG_NO_DRAIN | LDPC_SCHED_DEBUG_BAD_LANE;
 
 // flags_set bits of a resolved schedule, outside kAllFlags: resolved, and
@@ -127,6 +128,7 @@ Engine::~Engine()
     if (h_fault) hipHostFree(h_fault);
     hipFree(d_row_ptr); hipFree(d_col_idx); hipFree(d_col_idx_T); hipFree(d_col_ptr); hipFree(d_col_edge); hipFree(d_col_er); hipFree(d_row_pos);
     hipFree(d_unsat); hipFree(d_done); hipFree(d_fin); hipFree(d_fin_b); hipFree(d_fin_n);
+    hipFree(d_ho); hipFree(d_pend_b); hipFree(hard_fin);
     hipFree(d_sgn);
     hipFree(v2c); if (c2v != v2c) hipFree(c2v); hipFree(prior); hipFree(hard); hipFree(active); hipFree(iters); hipFree(valid);
     hipFree(post_t);
@@ -230,6 +232,9 @@ int Engine::init(const HostGraph* graph, int dev, int algorithm, int64_t chunk, 
         64.0 * 8.0 * kDefaultPoolTiles * ((double)g->E + (double)g->N) > 1.15 * kGenPoolBytes)
         res = false;
     nt_d = sched_flag(sched, LDPC_SCHED_NONTEMPORAL) && !res;  // the pool is meant to stay cached
+    // hand-over: k_check_bp / k_check_msa<72, ., RES> + k_var_m in place only
+    handover = sched_flag(sched, LDPC_SCHED_HANDOVER) && res && reg_72_8 &&
+               (algo == LDPC_ALGO_BP || algo == LDPC_ALGO_MSA);
     debug_no_drain = sched_flag(sched, LDPC_SCHED_DEBUG_NO_DRAIN);
     debug_bad_lane = sched_flag(sched, LDPC_SCHED_DEBUG_BAD_LANE);
     var_cpw = sched.var_cpw;
@@ -308,6 +313,11 @@ int Engine::init(const HostGraph* graph, int dev, int algorithm, int64_t chunk, 
         LDPC_HIP(hipMalloc((void**)&d_fin, (size_t)cap_tiles * sizeof(uint64_t)));
         LDPC_HIP(hipMalloc((void**)&d_fin_b, (size_t)cap * sizeof(int64_t)));
         LDPC_HIP(hipMalloc((void**)&d_fin_n, (size_t)cap * sizeof(int32_t)));
+        if (handover) {
+            LDPC_HIP(hipMalloc((void**)&d_ho, (size_t)cap_tiles * 3 * sizeof(uint64_t)));
+            LDPC_HIP(hipMalloc((void**)&d_pend_b, (size_t)cap * sizeof(int64_t)));
+            LDPC_HIP(hipMalloc((void**)&hard_fin, (size_t)cap_tiles * g->N * sizeof(uint64_t)));
+        }
         // grouped continuous schedule: a separate syndrome launch spread over
         // several blocks per tile (the resident pool fuses it into the check)
         syn_blocks = res ? 0 : sched.syn_blocks;
@@ -341,6 +351,7 @@ int32_t Engine::flags() const
     return (nt_d ? LDPC_SCHED_NONTEMPORAL : 0) | (cont ? LDPC_SCHED_CONTINUOUS : 0) |
            (msa_c ? LDPC_SCHED_MSA_COMPRESSED : 0) | (res ? LDPC_SCHED_RESIDENT : 0) |
            (syn_blocks > 0 ? LDPC_SCHED_SPLIT_SYNDROME : 0) | (first_fp ? LDPC_SCHED_FIRST_FROM_PRIOR : 0) |
+           (handover ? LDPC_SCHED_HANDOVER : 0) |
            (sched.flags & (LDPC_SCHED_LR_TABLE | LDPC_SCHED_DEBUG_NO_DRAIN | LDPC_SCHED_DEBUG_BAD_LANE));
 }
 
@@ -1061,7 +1072,7 @@ int Engine::run_cont_steps(const double* d_in, int in_kind, int64_t B, int32_t m
     // lane masks, claim counter + occupancy ring and the syndrome words in one launch
     static_assert(1 + kRing <= 256, "occupancy ring");
     LAUNCH(K_OTHER, klaunch(k_cont_reset, dim3((unsigned)std::min<int64_t>((tiles + 255) / 256, 1024)), dim3(256), 0,
-                            stream, active, d_fresh, d_occ, d_ctr, 1 + kRing, d_unsat, d_done, tiles));
+                            stream, active, d_fresh, d_occ, d_ctr, 1 + kRing, d_unsat, d_done, tiles, d_ho, cap_tiles));
     ContState cs{active, d_fresh, d_occ, d_lane_b, d_lane_n, d_ctr, nullptr, B};
     cs.ntiles = tiles;
     cs.fault = d_fault;
@@ -1075,6 +1086,16 @@ int Engine::run_cont_steps(const double* d_in, int in_kind, int64_t B, int32_t m
               d_hard, d_post, post_kind == LDPC_POST_RATIO ? 1 : 0, hard_vec};
     rf.nb = B;
     rf.fault = d_fault;
+    if (handover) {
+        rs.last = d_ho;
+        rs.pend = d_ho + cap_tiles;
+        rs.unsat_fin = reinterpret_cast<unsigned long long*>(d_ho + 2 * cap_tiles);
+        rs.pend_b = d_pend_b;
+        rs.hard_fin = hard_fin;
+        rf.last = rs.last;
+        rf.pend_b = d_pend_b;
+        rf.hard_fin = hard_fin;
+    }
     if (cur_codes) {  // coded input (decode_codes): int8 priors
         rf.in = nullptr;
         rf.in_code = cur_codes;

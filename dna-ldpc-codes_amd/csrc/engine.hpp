@@ -52,6 +52,7 @@ struct Engine {
     bool msa_c = false;       // min-sum with compressed c2v (records + meta words, k_check_msa_c / k_var_msa_c)
     bool res = false;         // resident pool: a few tiles iterated in place, syndrome in the check kernel
     bool first_fp = false;    // single-fill BP: the first check reads the prior (k_check_bp_first)
+    bool handover = false;    // res, (8,72)-regular: a lane is refilled during its codeword's last update (ResStep::last)
     bool debug_no_drain = false;  // LDPC_SCHED_DEBUG_NO_DRAIN: the host ignores a drained pool
     bool debug_bad_lane = false;  // LDPC_SCHED_DEBUG_BAD_LANE: one lane records an out-of-range codeword index
     int var_cpw = 4;          // variable phase: columns per wave (-2: by the prior's form, var_cpw_for)
@@ -63,6 +64,11 @@ struct Engine {
     uint64_t* d_fin = nullptr;              // [tile] lanes finished at the step
     int64_t* d_fin_b = nullptr;             // [tile*64] their codeword index
     int32_t* d_fin_n = nullptr;             // [tile*64] their iteration count
+    // handover: [0, cap_tiles) last, [cap_tiles, 2 cap_tiles) pend, [2 cap_tiles, 3 cap_tiles) the pending
+    // plane's syndrome words; the pending codewords' indices; the second ballot plane [tile][N]
+    uint64_t* d_ho = nullptr;
+    int64_t* d_pend_b = nullptr;
+    uint64_t* hard_fin = nullptr;
     const dev::ResStep* rstep = nullptr;    // res: set around the check launch of a step
     static constexpr int kRing = 8, kLag = 2;
     uint64_t* d_fresh = nullptr;

@@ -37,6 +37,10 @@ struct Refill {
     // a violation skips the access and is reported through `fault`
     int64_t nb = 0;
     unsigned long long* fault = nullptr;
+    // hand-over (LDPC_SCHED_HANDOVER, resident pool; nullptr: off), see ResStep
+    const uint64_t* last = nullptr;   // [tile] lanes doing their codeword's final update this step
+    const int64_t* pend_b = nullptr;  // [tile*64] that codeword's index (its outputs are written by this step)
+    uint64_t* hard_fin = nullptr;     // [tile][N] ballots of the final updates
 };
 
 // Device fault words (pinned host memory, device-mapped; ContState / Refill
@@ -107,6 +111,19 @@ struct ResStep {
     ContState cs;
     ContOut co;                  // iters / valid (hard / post are written by the variable kernel)
     const int32_t* row_ptr = nullptr;  // [M+1] CSR row starts (k_syndrome_split_gen: any row degrees)
+    // Hand-over (LDPC_SCHED_HANDOVER; nullptr: off).  A lane whose codeword
+    // enters its max_iter-th update ends after this step's variable phase
+    // whatever its last syndrome says, so the bookkeeping claims its next
+    // codeword one step early (`last`); the variable kernel writes the old
+    // codeword's outputs from the final update, puts its ballots into
+    // hard_fin and initialises the new codeword in the same launch.  The next
+    // check takes the parity of both planes (hard_fin masked by `pend`, into
+    // unsat_fin) and its bookkeeping writes iters / valid of pend_b.
+    uint64_t* last = nullptr;                 // [tile] -> Refill::last
+    uint64_t* pend = nullptr;                 // [tile] lanes whose previous codeword's last syndrome is due
+    int64_t* pend_b = nullptr;                // [tile*64] that codeword's index
+    const uint64_t* hard_fin = nullptr;       // [tile][N] second ballot plane
+    unsigned long long* unsat_fin = nullptr;  // [tile] OR of the row parities over hard_fin & pend
 };
 
 }  // namespace dev

@@ -165,13 +165,31 @@ __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x)
 // ln0 / b0: the lane's cs.lane_n / cs.lane_b, loaded by the caller (only
 // meaningful for occupied lanes).  probe: read the claim counter before
 // claiming (avoids atomics on it once the input is exhausted).
+// ho (hand-over, ResStep::last; nullptr: off): a continuing lane that enters
+// its max_iter-th update ends after this step's variable phase whatever its
+// last syndrome says, so it claims its next codeword here (`last`: in active,
+// and in fresh when the claim succeeds; its finished index moves to pend_b).
+// That syndrome arrives with the next check (pend = the previous step's
+// last, Up = its parities over ResStep::hard_fin), whose bookkeeping writes
+// iters / valid of pend_b -- also for a lane that found the input drained and
+// left `occupied`: the occupancy word still counts a last lane at its own
+// step, so the host reads "empty" no earlier than from the step that wrote
+// the pending codeword's flags.
 __device__ __forceinline__ void cont_lanes(int64_t t, uint64_t occ, uint64_t U, int32_t max_iter, const ContState& cs,
                                            const ContOut& co, int64_t* s_b, int32_t* s_n, uint64_t* s_fin,
-                                           int32_t ln0, int64_t b0, bool probe)
+                                           int32_t ln0, int64_t b0, bool probe, const ResStep* ho = nullptr,
+                                           uint64_t pend = 0, uint64_t Up = 0)
 {
     const int lane = lane_id();
     {
         const size_t li = (size_t)t * TILE + lane;
+        if (ho && ((pend >> lane) & 1ull)) {  // the previous codeword's last syndrome
+            const int64_t pb = ho->pend_b[li];
+            if (lane_index_ok(pb, cs.B, cs.fault, kFaultIters)) {
+                co.iters[pb] = max_iter;
+                co.valid[pb] = ((Up >> lane) & 1ull) ? 0 : 1;
+            }
+        }
         const bool o = (occ >> lane) & 1ull;
         const int32_t ln = o ? ln0 : 0;
         const bool unsat = (U >> lane) & 1ull;
@@ -181,9 +199,10 @@ __device__ __forceinline__ void cont_lanes(int64_t t, uint64_t occ, uint64_t U, 
         if (fin && lane_index_ok(b, cs.B, cs.fault, kFaultIters)) { co.iters[b] = ln; co.valid[b] = unsat ? 0 : 1; }
         s_b[lane] = b;
         s_n[lane] = ln;
-        const uint64_t F = __ballot(fin), Cm = __ballot(cont);
-        // refill every lane that is not continuing
-        const uint64_t freem = ~Cm;
+        const bool last = ho && cont && ln + 1 == max_iter;
+        const uint64_t F = __ballot(fin), Cm = __ballot(cont), Lm = __ballot(last);
+        // refill every lane that is not continuing (hand-over: or ends with this step)
+        const uint64_t freem = ~Cm | Lm;
         const int nfree = __popcll(freem);
         unsigned long long base = 0;
         if (lane == 0 && nfree > 0) {
@@ -196,9 +215,10 @@ __device__ __forceinline__ void cont_lanes(int64_t t, uint64_t occ, uint64_t U, 
         }
         base = __shfl(base, 0);
         const int rank = __popcll(freem & ((1ull << lane) - 1ull));
-        const bool fresh = !cont && (base + (unsigned long long)rank < (unsigned long long)cs.B);
+        const bool fresh = (!cont || last) && (base + (unsigned long long)rank < (unsigned long long)cs.B);
         const uint64_t Fr = __ballot(fresh);
         if (cont) cs.lane_n[li] = ln + 1;
+        if (last) ho->pend_b[li] = b;
         if (fresh) {
             int64_t nbv = (int64_t)(base + rank);
             if (cs.debug_bad_lane && nbv == 0) nbv = cs.B + 4096;  // tests only (LDPC_SCHED_DEBUG_BAD_LANE)
@@ -208,7 +228,8 @@ __device__ __forceinline__ void cont_lanes(int64_t t, uint64_t occ, uint64_t U, 
         if (lane == 0) {
             cs.active[t] = Cm;
             cs.fresh[t] = Fr;
-            cs.occupied[t] = Cm | Fr;
+            cs.occupied[t] = (Cm & ~Lm) | Fr;  // a last lane without a claim holds no codeword after this step
+            if (ho) { ho->last[t] = Lm; ho->pend[t] = Lm; }
             *s_fin = F;
             if (cs.occ_count) {
                 const unsigned long long add = (1ull << kOccTileShift) | (unsigned long long)__popcll(Cm | Fr);
@@ -238,21 +259,44 @@ __device__ __forceinline__ uint64_t row_parity(const uint64_t* __restrict__ h, c
     return p;
 }
 
+// Hand-over (ResStep::pend): the lanes of tile t whose previous codeword's
+// last syndrome is due in this check, and a row's parity for them over the
+// second ballot plane (ResStep::hard_fin).  k_check_bp takes it after the
+// row's messages are stored, as a wave-uniform arm of its own: the steps
+// without a pending lane (all but one in max_iter) issue exactly the
+// instructions they did without it, and the one with pays the gathers'
+// latency once per wave.  Gathering the plane next to the current one's
+// ballots, ahead of the arithmetic, lost its A/B: the arm in the middle of
+// the row costs every step more than the tail costs the pending one
+// (profiles/r7/handover/README.md).
+__device__ __forceinline__ uint64_t pend_lanes(const ResStep& rs, int64_t t) { return rs.pend ? rs.pend[t] : 0ull; }
+template <int DC>
+__device__ __forceinline__ uint64_t pend_parity(const ResStep& rs, int64_t t, int32_t row, int32_t M, uint64_t pend)
+{
+    if (pend == 0 || row >= M) return 0ull;
+    return row_parity<DC>(rs.hard_fin + (size_t)t * rs.N, rs.col_idx + (size_t)row * DC) & pend;
+}
+
 // Resident pool epilogue of a check block (all 256 threads): OR the block's
 // row parities into unsat[t]; the last of the tile's nblk blocks to arrive runs the
 // lane bookkeeping for the step (cont_lanes: iters / valid, refill claims,
 // active / fresh / occupied masks) and hands the finished lanes to the
 // variable kernel, which writes their outputs before refilling them.
+// Hand-over (the callers that pass pend, ResStep::pend[t]): pp is the wave's
+// row parity over the pending plane (pend_parity), ORed into unsat_fin[t].
 __device__ __forceinline__ void res_arrive(int64_t t, uint64_t occ, uint64_t p, const ResStep& rs, int32_t ln0,
-                                           int64_t b0, uint32_t nblk)
+                                           int64_t b0, uint32_t nblk, uint64_t pend = 0, uint64_t pp = 0)
 {
-    __shared__ uint64_t red[4];
+    __shared__ uint64_t red[4], redp[4];
     __shared__ int64_t s_b[TILE];
     __shared__ int32_t s_n[TILE];
     __shared__ uint64_t s_fin;
     __shared__ int s_last;
     const int lane = lane_id(), w = wave_id();
-    if (lane == 0) red[w] = p;
+    if (lane == 0) {
+        red[w] = p;
+        redp[w] = pp;
+    }
     __syncthreads();
     // No fences: an agent-scope release would write back the L2 in every
     // block.  Only device-coherent atomics carry data between the blocks; the
@@ -263,6 +307,10 @@ __device__ __forceinline__ void res_arrive(int64_t t, uint64_t occ, uint64_t p, 
         const uint64_t U = red[0] | red[1] | red[2] | red[3];
         unsigned long long o = 0;
         if (U) o = atomicOr(rs.unsat + t, (unsigned long long)U);
+        if (pend) {
+            const uint64_t Up = redp[0] | redp[1] | redp[2] | redp[3];
+            if (Up) o |= atomicOr(rs.unsat_fin + t, (unsigned long long)Up);
+        }
         asm volatile("" ::"v"(o) : "memory");
         s_last = atomicAdd(rs.done + t, 1u) == nblk - 1;
     }
@@ -270,13 +318,16 @@ __device__ __forceinline__ void res_arrive(int64_t t, uint64_t occ, uint64_t p, 
     if (!s_last) return;
     if (threadIdx.x < TILE) {
         const uint64_t U = occ ? (uint64_t)atomicOr(rs.unsat + t, 0ull) : 0ull;
-        cont_lanes(t, occ, U, rs.max_iter, rs.cs, rs.co, s_b, s_n, &s_fin, ln0, b0, false);
+        const uint64_t Up = pend ? (uint64_t)atomicOr(rs.unsat_fin + t, 0ull) : 0ull;
+        cont_lanes(t, occ, U, rs.max_iter, rs.cs, rs.co, s_b, s_n, &s_fin, ln0, b0, false, rs.last ? &rs : nullptr, pend,
+                   Up);
         const size_t li = (size_t)t * TILE + lane;
         rs.fin_b[li] = s_b[lane];
         rs.fin_n[li] = s_n[lane];
         if (lane == 0) {
             rs.fin[t] = s_fin;
             atomicExch(rs.unsat + t, 0ull);
+            if (pend) atomicExch(rs.unsat_fin + t, 0ull);
             atomicExch(rs.done + t, 0u);
         }
     }
@@ -488,6 +539,7 @@ __device__ __forceinline__ void check_bp_block(typename Msg<RES>::in dmsg, typen
         // on an occupied tile only), loaded up front off the tail's chain
         const int32_t ln0 = rs.cs.lane_n[t * TILE + lane];
         const int64_t b0 = rs.cs.lane_b[t * TILE + lane];
+        const uint64_t pend = pend_lanes(rs, t);
         uint64_t par = 0;
         if (row < M && act != 0) {
             const int32_t* __restrict__ cols = rs.col_idx + (size_t)row * DC;
@@ -508,7 +560,7 @@ __device__ __forceinline__ void check_bp_block(typename Msg<RES>::in dmsg, typen
             for (int off = 32; off > 0; off >>= 1) p ^= shfl_xor_u64(p, off);
             par = p;
         }
-        res_arrive(t, act, par, rs, occ_l ? ln0 : 0, occ_l ? b0 : 0, nrb);
+        res_arrive(t, act, par, rs, occ_l ? ln0 : 0, occ_l ? b0 : 0, nrb, pend, pend_parity<DC>(rs, t, row, M, pend));
     }
 }
 
@@ -671,6 +723,9 @@ __device__ __forceinline__ double prior_at(const double* __restrict__ prior, con
 // CONT: refilled lanes (Refill::fresh) get Init_Belief_Propagation
 // (dec.cpp:608-629) / Init_MSA_INF (dec.cpp:1300-1329) through the same
 // stores, and finished lanes (Refill::fin) get their outputs written first.
+// CONT && INPLACE, hand-over (Refill::last): a lane in its codeword's final
+// update gets only P / L and the decision, its outputs written from them,
+// and, when it also is in `fresh`, Init for its next codeword.
 // INPLACE: v2c == c2v (resident pool), see Msg.  PC (coded input, CONT
 // only): the lanes' priors are int8 codes (Refill::pcode / ptab), refills
 // read the input's codes (Refill::in_code).
@@ -691,10 +746,15 @@ __device__ __forceinline__ void var_m_block(typename Msg<INPLACE>::in c2v_t, typ
     // resident pool: lanes whose codeword finished at this step's syndrome
     // (their outputs are written here, before a refill overwrites the lane)
     const uint64_t fm = (CONT && rf.fin) ? rf.fin[t] : 0ull;
+    // resident pool, hand-over (Refill::last, a subset of `active`): lanes
+    // whose codeword gets its final update in this step
+    constexpr bool HO = CONT && INPLACE;
+    const uint64_t lastm = (HO && rf.last) ? rf.last[t] : 0ull;
     if (touched == 0 && fm == 0) return;
     const bool live = (act >> lane) & 1ull;
     const bool fr = CONT && ((frm >> lane) & 1ull);
     const bool fl = (fm >> lane) & 1ull;
+    const bool ls = HO && ((lastm >> lane) & 1ull);
     int64_t fb = 0;
     int32_t fn = 0;
     if (fl) {
@@ -736,6 +796,41 @@ __device__ __forceinline__ void var_m_block(typename Msg<INPLACE>::in c2v_t, typ
 #pragma unroll
             for (int c = 0; c < CPW; ++c) xin[c] = rf.ptab[kin[c] + kCodeBias];
         }
+    }
+    if (HO && lastm != 0) {
+        // Hand-over, a wave-uniform arm taken in one step of max_iter: a last
+        // lane's codeword ends with this update whatever its syndrome will
+        // say, so only the update's P / L and decision are computed (the
+        // update branch's expressions), the codeword's outputs are written
+        // from them here, and its ballots go to the second plane, whose
+        // parity the next check takes (ResStep::pend).  The lane's slot in
+        // `hard` and its messages belong to its next codeword (fr, below).
+        const int64_t lb = ls ? rf.pend_b[t * TILE + lane] : 0;
+        const bool lok = out_ok(lb, rf);
+        uint64_t hwf[CPW];
+#pragma unroll
+        for (int c = 0; c < CPW; ++c) {
+            bool hf = false;
+            if (ls) {
+                double p = pv[c];
+                if (MSA) {
+#pragma unroll
+                    for (int s = 0; s < DV; ++s) p = p + l[c][s];
+                    hf = !(p > 0);
+                    if (lok && rf.post_out) rf.post_out[(size_t)lb * N + j0 + c] = p;
+                } else {
+#pragma unroll
+                    for (int s = 0; s < DV; ++s) p = p * l[c][s];
+                    if (__builtin_isnan(p)) p = 1.0;
+                    hf = (p <= 1.0);
+                    if (lok && rf.post_out) rf.post_out[(size_t)lb * N + j0 + c] = rf.post_ratio ? p : log(p);
+                }
+            }
+            hwf[c] = __ballot(hf);
+            if (lane == 0) rf.hard_fin[(size_t)t * N + j0 + c] = hwf[c];
+        }
+        if (ls && lok) store_fin_hard<CPW>(rf, hwf, lb, N, j0, lane);
+        if (ls && !lok) lane_fault(rf.fault, kFaultOutput, t * TILE + lane);
     }
     // the finished codeword's index bounds: a plain compare at the stores
     // (a check with its fault report where fin_b is loaded makes every wave
@@ -783,7 +878,7 @@ __device__ __forceinline__ void var_m_block(typename Msg<INPLACE>::in c2v_t, typ
                 for (int s = 0; s < DV; ++s) dv[s] = d0;
                 h = (LR0 < 1.0);
             }
-        } else if (live) {
+        } else if (live && !ls) {
             if (MSA) {  // v2c_s = LLR + c_0 + ... (skipping c_s); L = LLR + all
 #pragma unroll
                 for (int s = 0; s < DV; ++s) {
@@ -968,6 +1063,7 @@ __global__ __launch_bounds__(256) void k_check_msa(typename Msg<RES>::in v2c, ty
     uint64_t par = 0;
     int32_t ln0 = 0;
     int64_t b0 = 0;
+    const uint64_t pend = RES ? pend_lanes(rs, t) : 0ull;
     if (RES && act != 0) {
         // the lane state for res_arrive's bookkeeping (used by the tile's last
         // block only), loaded up front so it is not on the tail's chain
@@ -976,11 +1072,12 @@ __global__ __launch_bounds__(256) void k_check_msa(typename Msg<RES>::in v2c, ty
             b0 = rs.cs.lane_b[t * TILE + lane];
         }
         if (row < M) par = row_parity<DC>(rs.hard + (size_t)t * rs.N, rs.col_idx + (size_t)row * DC);
-    }
-    if (run)
+    }    if (run)
         check_msa_row<DC, NT, RES>(v2c + ((size_t)t * E + (size_t)row * DC) * TILE + lane,
                                    c2v + ((size_t)blockIdx.y * E + (size_t)row * DC) * TILE + lane);
-    if constexpr (RES) res_arrive(t, act, par, rs, ln0, b0, gridDim.x);
+    if constexpr (RES) {
+        res_arrive(t, act, par, rs, ln0, b0, gridDim.x, pend, pend_parity<DC>(rs, t, row, M, pend));
+    }
 }
 
 __global__ __launch_bounds__(256) void k_check_msa_gen(const double* __restrict__ v2c, double* __restrict__ c2v,
@@ -1925,7 +2022,8 @@ __global__ __launch_bounds__(256) void k_finalize(const double* __restrict__ pos
 __global__ __launch_bounds__(256) void k_cont_reset(uint64_t* __restrict__ active, uint64_t* __restrict__ fresh,
                                                     uint64_t* __restrict__ occupied, unsigned long long* __restrict__ ctr,
                                                     int32_t nctr, unsigned long long* __restrict__ unsat,
-                                                    unsigned* __restrict__ done, int64_t tiles)
+                                                    unsigned* __restrict__ done, int64_t tiles,
+                                                    uint64_t* __restrict__ ho, int64_t ho_stride)
 {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < tiles; i += (int64_t)gridDim.x * blockDim.x) {
         active[i] = 0;
@@ -1933,6 +2031,11 @@ __global__ __launch_bounds__(256) void k_cont_reset(uint64_t* __restrict__ activ
         occupied[i] = 0;
         if (unsat) unsat[i] = 0;
         if (done) done[i] = 0;
+        if (ho) {  // hand-over: last, pend and the pending plane's syndrome words (ho_stride apart)
+            ho[i] = 0;
+            ho[ho_stride + i] = 0;
+            ho[2 * ho_stride + i] = 0;
+        }
     }
     if (blockIdx.x == 0 && (int32_t)threadIdx.x < nctr) ctr[threadIdx.x] = 0;
 }

@@ -76,7 +76,7 @@ class LdpcError(RuntimeError):
 
 # ldpc_schedule flag bits (include/ldpc_amd.h LDPC_SCHED_*) by keyword
 SCHED_FLAGS = {"nontemporal": 1 << 0, "continuous": 1 << 3, "msa_compressed": 1 << 4, "resident": 1 << 5,
-               "split_syndrome": 1 << 6, "first_from_prior": 1 << 12, "lr_table": 1 << 13,
+               "split_syndrome": 1 << 6, "handover": 1 << 7, "first_from_prior": 1 << 12, "lr_table": 1 << 13,
                "debug_no_drain": 1 << 14, "debug_bad_lane": 1 << 15}
 SCHED_FIELDS = ("group_tiles", "var_cpw", "pool_tiles", "poll_every", "syn_blocks")
 
@@ -614,6 +614,7 @@ class Engine:
         self.resident = bool(f & SCHED_FLAGS["resident"])  # in-place pool of a few tiles
         self.syndrome_split = bool(f & SCHED_FLAGS["split_syndrome"])  # multi-block continuous-mode syndrome
         self.first_from_prior = bool(f & SCHED_FLAGS["first_from_prior"])
+        self.handover = bool(f & SCHED_FLAGS["handover"])  # resident pool: refill during a codeword's last update
 
     def decode(self, d_in, in_kind: int, B: int, max_iter: int, d_hard=None, d_post=None, post_kind=POST_LLR,
                d_iters=None, d_valid=None):

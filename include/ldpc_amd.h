@@ -95,6 +95,13 @@ enum {
                                            pool is chosen by the engine or is at most 4 tiles) */
     LDPC_SCHED_SPLIT_SYNDROME = 1 << 6, /* (ldpc_engine_info only) continuous grouped schedule: syndrome
                                            spread over syn_blocks blocks per tile */
+    LDPC_SCHED_HANDOVER = 1 << 7,       /* resident pool on (8,72)-regular graphs, BP / fp64 min-sum: a lane
+                                           whose codeword enters its max_iter-th update claims its next
+                                           codeword in that step; the variable kernel writes the finished
+                                           outputs and initialises the new codeword in one launch, and the
+                                           last syndrome (the valid flag) follows in the next check: max_iter
+                                           instead of max_iter + 1 steps per codeword that does not converge
+                                           (default on; off elsewhere) */
     LDPC_SCHED_FIRST_FROM_PRIOR = 1 << 12, /* single-fill BP decodes: the first check derives its messages
                                               from the prior instead of E stored copies (default on) */
     LDPC_SCHED_LR_TABLE = 1 << 13,      /* ldpc_decode, BP (host exp) and min-sum: LLR batches on a k * unit
