@@ -32,6 +32,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <thread>
+#include <type_traits>
+#include <utility>
 
 #include "engine.hpp"
 #include "kernels.hpp"
@@ -158,17 +160,47 @@ static uint16_t* msa_meta(double* scratch, int64_t tiles, int32_t M)
     return reinterpret_cast<uint16_t*>(scratch + (size_t)tiles * M * dev::MSA_REC_PLANES * dev::TILE);
 }
 
-// Degree buckets of the register-staged generic kernels (kernels.hpp *_gr):
+// Degree buckets of the register-staged generic kernels (kernels.hpp
+// k_check_gr / k_var_gr and their lane-pool forms), ascending.  Each list is
+// stated here only: gen_bucket and the launches (dispatch) both run over it.
+template <int... Ds>
+using Buckets = std::integer_sequence<int, Ds...>;
+using CheckBuckets = Buckets<8, 16, 32, 48, 64, 96>;
+using VarBuckets = Buckets<4, 8, 12, 16, 24, 32>;
+
 // the smallest bucket >= the graph's maximum degree, 0 when none holds it
 // (the memory-staged *_gen kernels then run; no continuous mode without a
-// variable bucket).
-static constexpr int kGenCheckBuckets[] = {8, 16, 32, 48, 64, 96, 0};
-static constexpr int kGenVarBuckets[] = {4, 8, 12, 16, 24, 32, 0};
-static int gen_bucket(int32_t dmax, const int* buckets)
+// variable bucket)
+template <int... Ds>
+static int gen_bucket(int32_t dmax, Buckets<Ds...>)
 {
-    for (const int* b = buckets; *b; ++b)
-        if (dmax <= *b) return *b;
-    return 0;
+    int b = 0;
+    (void)((dmax <= Ds && (b = Ds, true)) || ...);
+    return b;
+}
+
+// Run-time values to template arguments, the one mechanism of launch_check /
+// launch_var.  with_bools: f(std::bool_constant<b>...).  dispatch: the
+// member of the list equal to v first, f(std::integral_constant<int, v>,
+// std::bool_constant<b>...); false, and f not called, when the list has no
+// such member.  f is a generic lambda that names its kernel with D(), NT(), ...;
+// combinations that are not to exist it leaves out with `if constexpr`, so
+// they are not instantiated either.
+template <typename F>
+static void with_bools(F&& f)
+{
+    f();
+}
+template <typename F, typename... Bs>
+static void with_bools(F&& f, bool b, Bs... rest)
+{
+    if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+template <int... Vs, typename F, typename... Bs>
+static bool dispatch(int v, std::integer_sequence<int, Vs...>, F&& f, Bs... bs)
+{
+    return ((v == Vs && (with_bools([&](auto... cs) { f(std::integral_constant<int, Vs>{}, cs...); }, bs...), true)) || ...);
 }
 
 // Default resident pool of a code other than the (8, 72)-regular one: as many
@@ -211,14 +243,14 @@ int Engine::init(const HostGraph* graph, int dev, int algorithm, int64_t chunk, 
     // degrees fit a register bucket of the generic continuous variable kernel
     // (k_var_gr_cont; its syndrome k_syndrome_split_gen)
     cont = sched_flag(sched, LDPC_SCHED_CONTINUOUS) && !int_algo &&
-           (reg_72_8 || (g->regular_dv && g->dv_max == 8) || gen_bucket(g->dv_max, kGenVarBuckets) != 0);
+           (reg_72_8 || (g->regular_dv && g->dv_max == 8) || gen_bucket(g->dv_max, VarBuckets{}) != 0);
     // resident pool: a few tiles whose whole state fits the
     // Infinity Cache, check->variable messages written over the variable->check
     // messages they are computed from (each row's / column's edges are read
     // into registers before its outputs are stored), no c2v scratch
     // (other codes: row and column degrees in register buckets, k_check_gr_res + k_var_gr_cont in place)
-    const bool gen_res = !reg_72_8 && gen_bucket(g->dc_max, kGenCheckBuckets) != 0 &&
-                         gen_bucket(g->dv_max, kGenVarBuckets) != 0;
+    const bool gen_res = !reg_72_8 && gen_bucket(g->dc_max, CheckBuckets{}) != 0 &&
+                         gen_bucket(g->dv_max, VarBuckets{}) != 0;
     res = sched_flag(sched, LDPC_SCHED_RESIDENT) && cont && !msa_c && ((reg_72_8 && g->N % 32 == 0) || gen_res);
     // by default the resident pool is the Infinity-Cache-sized one: a caller's
     // explicit larger pool (the host API's chunks, the DNA batch) runs the
@@ -509,22 +541,13 @@ int Engine::launch_check(hipStream_t s, double* scratch, int64_t t0, unsigned gt
     const int64_t E = g->E;
     const bool reg72 = g->regular_dc && g->dc_max == 72;
     const dim3 grid((M + 3) / 4, gt), blk(256);
-    const int msa = algo == LDPC_ALGO_MSA;
+    const bool msa = algo == LDPC_ALGO_MSA;
     if (res && !reg72) {
-        if (!rstep || scratch != v2c || t0 != 0) { set_error("resident check: bad state"); return LDPC_ERR_ARG; }
-#define CHECK_RES(D)                                                                                            \
-    (msa ? klaunch((k_check_gr_res<true, D>), grid, blk, 0, s, v2c, d_row_ptr, M, E, *rstep)                   \
-         : klaunch((k_check_gr_res<false, D>), grid, blk, 0, s, v2c, d_row_ptr, M, E, *rstep))
-        const int cb = gen_bucket(g->dc_max, kGenCheckBuckets);
-        LAUNCH_ON(s, K_CHECK, {
-            if (cb == 8) CHECK_RES(8);
-            else if (cb == 16) CHECK_RES(16);
-            else if (cb == 32) CHECK_RES(32);
-            else if (cb == 48) CHECK_RES(48);
-            else if (cb == 64) CHECK_RES(64);
-            else CHECK_RES(96);
-        });
-#undef CHECK_RES
+        const int cb = gen_bucket(g->dc_max, CheckBuckets{});
+        if (!rstep || scratch != v2c || t0 != 0 || !cb) { set_error("resident check: bad state"); return LDPC_ERR_ARG; }
+        LAUNCH_ON(s, K_CHECK, dispatch(cb, CheckBuckets{}, [&](auto D, auto MSA) {
+            klaunch((k_check_gr_res<MSA(), D()>), grid, blk, 0, s, v2c, d_row_ptr, M, E, *rstep);
+        }, msa));
         return LDPC_OK;
     }
     if (res) {
@@ -537,79 +560,30 @@ int Engine::launch_check(hipStream_t s, double* scratch, int64_t t0, unsigned gt
     }
     if (msa_c) {  // 1-D XCD-affine grid (k_check_msa_c)
         const dim3 g1((unsigned)((M + 3) / 4) * gt);
-        if (nt_d)
-            LAUNCH_ON(s, K_CHECK, klaunch((k_check_msa_c<72, true>), g1, blk, 0, s, v2c, msa_rec(scratch),
-                                          msa_meta(scratch, c2v_tiles, M), active, d_row_pos, M, E, t0, gt));
-        else
-            LAUNCH_ON(s, K_CHECK, klaunch((k_check_msa_c<72, false>), g1, blk, 0, s, v2c, msa_rec(scratch),
-                                          msa_meta(scratch, c2v_tiles, M), active, d_row_pos, M, E, t0, gt));
+        LAUNCH_ON(s, K_CHECK, with_bools([&](auto NT) {
+            klaunch((k_check_msa_c<72, NT()>), g1, blk, 0, s, v2c, msa_rec(scratch), msa_meta(scratch, c2v_tiles, M),
+                    active, d_row_pos, M, E, t0, gt);
+        }, nt_d));
         return LDPC_OK;
     }
     if (reg72) {
         // scratch == v2c only in the resident pool's placement probe (timing)
-        LAUNCH_ON(s, K_CHECK, {
-            if (msa && nt_d) klaunch((k_check_msa<72, true, false>), grid, blk, 0, s, v2c, scratch, active, M, E, t0, ResStep{});
-            else if (msa) klaunch((k_check_msa<72, false, false>), grid, blk, 0, s, v2c, scratch, active, M, E, t0, ResStep{});
-            else if (nt_d) klaunch((k_check_bp<72, true, false>), grid, blk, 0, s, v2c, scratch, active, M, E, t0, ResStep{});
-            else klaunch((k_check_bp<72, false, false>), grid, blk, 0, s, v2c, scratch, active, M, E, t0, ResStep{});
-        });
+        LAUNCH_ON(s, K_CHECK, with_bools([&](auto NT) {
+            if (msa) klaunch((k_check_msa<72, NT(), false>), grid, blk, 0, s, v2c, scratch, active, M, E, t0, ResStep{});
+            else klaunch((k_check_bp<72, NT(), false>), grid, blk, 0, s, v2c, scratch, active, M, E, t0, ResStep{});
+        }, nt_d));
     } else {
         // generic row degrees: registers up to the bucket of dc_max, else memory
         const bool bp = algo == LDPC_ALGO_BP;
-#define CHECK_GR(D)                                                                                                 \
-    (bp ? klaunch(k_check_bp_gr<D>, grid, blk, 0, s, v2c, scratch, active, d_row_ptr, M, E, t0)                    \
-        : klaunch(k_check_msa_gr<D>, grid, blk, 0, s, v2c, scratch, active, d_row_ptr, M, E, t0))
         LAUNCH_ON(s, K_CHECK, {
-            switch (gen_bucket(g->dc_max, kGenCheckBuckets)) {
-                case 8: CHECK_GR(8); break;
-                case 16: CHECK_GR(16); break;
-                case 32: CHECK_GR(32); break;
-                case 48: CHECK_GR(48); break;
-                case 64: CHECK_GR(64); break;
-                case 96: CHECK_GR(96); break;
-                default:
-                    if (bp) klaunch(k_check_bp_gen, grid, blk, 0, s, v2c, scratch, active, d_row_ptr, M, E, t0);
-                    else klaunch(k_check_msa_gen, grid, blk, 0, s, v2c, scratch, active, d_row_ptr, M, E, t0);
-            }
+            const bool in_regs = dispatch(gen_bucket(g->dc_max, CheckBuckets{}), CheckBuckets{}, [&](auto D, auto MSA) {
+                klaunch(k_check_gr<MSA(), D()>, grid, blk, 0, s, v2c, scratch, active, d_row_ptr, M, E, t0);
+            }, !bp);
+            if (!in_regs && bp) klaunch(k_check_bp_gen, grid, blk, 0, s, v2c, scratch, active, d_row_ptr, M, E, t0);
+            else if (!in_regs) klaunch(k_check_msa_gen, grid, blk, 0, s, v2c, scratch, active, d_row_ptr, M, E, t0);
         });
-#undef CHECK_GR
     }
     return LDPC_OK;
-}
-
-template <bool MSA, bool NT, bool CONT, bool INPLACE, bool PC = false>
-static void var_m_cpw(int cpw, hipStream_t s, dim3 grid, const double* c2v, double* v2c, double* prior, uint64_t* hard,
-                      const uint64_t* active, const int32_t* col_edge, double* pt, int32_t N, int64_t E, int64_t t0,
-                      const dev::Refill& rf)
-{
-    using namespace dev;
-    if (cpw == 8)
-        klaunch((k_var_m<MSA, 8, NT, CONT, 8, INPLACE, PC>), grid, dim3(256), 0, s, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-    else if (cpw == 4)
-        klaunch((k_var_m<MSA, 8, NT, CONT, 4, INPLACE, PC>), grid, dim3(256), 0, s, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-    else if (cpw == 2)
-        klaunch((k_var_m<MSA, 8, NT, CONT, 2, INPLACE, PC>), grid, dim3(256), 0, s, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-    else
-        klaunch((k_var_m<MSA, 8, NT, CONT, 1, INPLACE, PC>), grid, dim3(256), 0, s, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-}
-
-// PC: coded priors (continuous refills only: rf.in_code set)
-template <bool MSA>
-static void var_m(bool nt, bool cont, bool inplace, int cpw, hipStream_t s, dim3 grid, const double* c2v, double* v2c,
-                  double* prior, uint64_t* hard, const uint64_t* active, const int32_t* col_edge, double* pt, int32_t N,
-                  int64_t E, int64_t t0, const dev::Refill& rf)
-{
-    const bool pc = cont && rf.in_code != nullptr;
-    // in place (the resident pool, or its placement probe) is never nontemporal
-    if (inplace && pc) var_m_cpw<MSA, false, true, true, true>(cpw, s, grid, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-    else if (inplace && cont) var_m_cpw<MSA, false, true, true>(cpw, s, grid, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-    else if (inplace) var_m_cpw<MSA, false, false, true>(cpw, s, grid, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-    else if (nt && pc) var_m_cpw<MSA, true, true, false, true>(cpw, s, grid, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-    else if (nt && cont) var_m_cpw<MSA, true, true, false>(cpw, s, grid, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-    else if (nt) var_m_cpw<MSA, true, false, false>(cpw, s, grid, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-    else if (pc) var_m_cpw<MSA, false, true, false, true>(cpw, s, grid, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-    else if (cont) var_m_cpw<MSA, false, true, false>(cpw, s, grid, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
-    else var_m_cpw<MSA, false, false, false>(cpw, s, grid, c2v, v2c, prior, hard, active, col_edge, pt, N, E, t0, rf);
 }
 
 // columns per variable-phase wave: the schedule's, or by default 2 for coded
@@ -630,104 +604,54 @@ int Engine::launch_var(hipStream_t s, double* scratch, int64_t t0, unsigned gt, 
     const int64_t E = g->E;
     const bool reg8 = g->regular_dv && g->dv_max == 8;
     const bool cnt = rf.fresh != nullptr;
+    const bool pc = cnt && rf.in_code != nullptr;  // coded priors (continuous refills only)
+    const bool inplace = scratch == v2c;           // the resident pool, or its placement probe
+    bool ok = true;  // the columns per wave / the degree have a kernel
     if (msa_c) {  // N % 16 == 0 (init)
         int cpw = std::min(var_cpw_for(rf), 4);
         if (N % (4 * cpw) != 0) cpw = 1;  // (N % 16 == 0: every CPW but 3 divides)
         const unsigned nb = gt * (unsigned)(N / (4 * cpw));
         const double* rec = msa_rec(scratch);
         const uint16_t* meta = msa_meta(scratch, c2v_tiles, M);
-#define VAR_MSA_C3(CONT, CPW, NT, PC)                                                                                \
-    klaunch((k_var_msa_c<72, 8, CONT, CPW, NT, PC>), dim3(nb), dim3(256), 0, s, rec, meta, v2c, prior, hard, d_sgn, \
-            active, d_col_er, pt, N, M, E, t0, (uint32_t)gt, msa_pa, msa_pb, rf)
-#define VAR_MSA_C2(CONT, CPW, NT)                                   \
-    do {                                                            \
-        if (CONT && rf.in_code) VAR_MSA_C3(CONT, CPW, NT, CONT);    \
-        else VAR_MSA_C3(CONT, CPW, NT, false);                      \
-    } while (0)
-#define VAR_MSA_C(CONT, CPW)              \
-    do {                                  \
-        if (nt_d) VAR_MSA_C2(CONT, CPW, true); \
-        else VAR_MSA_C2(CONT, CPW, false);     \
-    } while (0)
-        LAUNCH_ON(s, K_VAR, {
-            if (cnt && cpw == 4) VAR_MSA_C(true, 4);
-            else if (cnt && cpw == 3) VAR_MSA_C(true, 3);
-            else if (cnt && cpw == 2) VAR_MSA_C(true, 2);
-            else if (cnt) VAR_MSA_C(true, 1);
-            else if (cpw == 4) VAR_MSA_C(false, 4);
-            else if (cpw == 3) VAR_MSA_C(false, 3);
-            else if (cpw == 2) VAR_MSA_C(false, 2);
-            else VAR_MSA_C(false, 1);
-        });
-#undef VAR_MSA_C
-#undef VAR_MSA_C2
-#undef VAR_MSA_C3
-        return LDPC_OK;
-    }
-    if (reg8) {
-        const bool inplace = scratch == v2c;
+        LAUNCH_ON(s, K_VAR, ok = dispatch(cpw, std::integer_sequence<int, 1, 2, 3, 4>{}, [&](auto CPW, auto CONT, auto NT, auto PC) {
+            if constexpr (CONT() || !PC())
+                klaunch((k_var_msa_c<72, 8, CONT(), CPW(), NT(), PC()>), dim3(nb), dim3(256), 0, s, rec, meta, v2c, prior,
+                        hard, d_sgn, active, d_col_er, pt, N, M, E, t0, (uint32_t)gt, msa_pa, msa_pb, rf);
+        }, cnt, nt_d, pc));
+    } else if (reg8) {
         const int want = var_cpw_for(rf);
         const int cpw = (want != 3 && N % (4 * want) == 0) ? want : 1;
         const dim3 grid((unsigned)((N + 4 * cpw - 1) / (4 * cpw)), gt);
-        LAUNCH_ON(s, K_VAR, {
-            if (algo == LDPC_ALGO_MSA) var_m<true>(nt_d, cnt, inplace, cpw, s, grid, scratch, v2c, prior, hard, active, d_col_edge, pt, N, E, t0, rf);
-            else var_m<false>(nt_d, cnt, inplace, cpw, s, grid, scratch, v2c, prior, hard, active, d_col_edge, pt, N, E, t0, rf);
-        });
-        return LDPC_OK;
-    }
-    const dim3 grid((N + 3) / 4, gt), blk(256);
-    // generic column degrees: registers up to the bucket of dv_max, else memory
-    const int vb = gen_bucket(g->dv_max, kGenVarBuckets);
-    if (cnt) {
-        if (!vb) { set_error("continuous mode needs column degrees <= 32"); return LDPC_ERR_ARG; }
-        const bool pc = rf.in_code != nullptr;
-        const bool inplace = scratch == v2c;  // the resident pool
-#define VAR_GRC3(MSA, D, PC)                                                                                         \
-    (inplace ? klaunch((k_var_gr_cont<MSA, D, PC, true>), grid, blk, 0, s, scratch, v2c, prior, hard, active,       \
-                       d_col_ptr, d_col_edge, pt, N, E, t0, rf)                                                      \
-             : klaunch((k_var_gr_cont<MSA, D, PC, false>), grid, blk, 0, s, scratch, v2c, prior, hard, active,      \
-                       d_col_ptr, d_col_edge, pt, N, E, t0, rf))
-#define VAR_GRC2(MSA, D) (pc ? VAR_GRC3(MSA, D, true) : VAR_GRC3(MSA, D, false))
-#define VAR_GRC(D)                          \
-    do {                                    \
-        if (algo == LDPC_ALGO_MSA) VAR_GRC2(true, D); \
-        else VAR_GRC2(false, D);            \
-    } while (0)
-        LAUNCH_ON(s, K_VAR, {
-            if (vb == 4) VAR_GRC(4);
-            else if (vb == 8) VAR_GRC(8);
-            else if (vb == 12) VAR_GRC(12);
-            else if (vb == 16) VAR_GRC(16);
-            else if (vb == 24) VAR_GRC(24);
-            else VAR_GRC(32);
-        });
-#undef VAR_GRC
-#undef VAR_GRC2
-#undef VAR_GRC3
-        return LDPC_OK;
-    }
-    if (vb) {
+        // in place is never nontemporal
+        LAUNCH_ON(s, K_VAR, ok = dispatch(cpw, std::integer_sequence<int, 1, 2, 4, 8>{},
+                                          [&](auto CPW, auto MSA, auto NT, auto CONT, auto IP, auto PC) {
+            if constexpr (!(IP() && NT()) && (CONT() || !PC()))
+                klaunch((k_var_m<MSA(), 8, NT(), CONT(), CPW(), IP(), PC()>), grid, dim3(256), 0, s, scratch, v2c, prior,
+                        hard, active, d_col_edge, pt, N, E, t0, rf);
+        }, algo == LDPC_ALGO_MSA, nt_d && !inplace, cnt, inplace, pc));
+    } else {
+        const dim3 grid((N + 3) / 4, gt), blk(256);
+        // generic column degrees: registers up to the bucket of dv_max, else memory
+        const int vb = gen_bucket(g->dv_max, VarBuckets{});
         const bool bp = algo == LDPC_ALGO_BP;
-#define VAR_GR(D)                                                                                                   \
-    (bp ? klaunch(k_var_bp_gr<D>, grid, blk, 0, s, scratch, v2c, prior, hard, active, d_col_ptr, d_col_edge, pt, N, \
-                  E, t0)                                                                                            \
-        : klaunch(k_var_msa_gr<D>, grid, blk, 0, s, scratch, v2c, prior, hard, active, d_col_ptr, d_col_edge, pt,   \
-                  N, E, t0))
-        LAUNCH_ON(s, K_VAR, {
-            if (vb == 4) VAR_GR(4);
-            else if (vb == 8) VAR_GR(8);
-            else if (vb == 12) VAR_GR(12);
-            else if (vb == 16) VAR_GR(16);
-            else if (vb == 24) VAR_GR(24);
-            else VAR_GR(32);
-        });
-#undef VAR_GR
-        return LDPC_OK;
+        if (cnt) {
+            if (!vb) { set_error("continuous mode needs column degrees <= 32"); return LDPC_ERR_ARG; }
+            LAUNCH_ON(s, K_VAR, dispatch(vb, VarBuckets{}, [&](auto D, auto MSA, auto PC, auto IP) {
+                klaunch((k_var_gr_cont<MSA(), D(), PC(), IP()>), grid, blk, 0, s, scratch, v2c, prior, hard, active,
+                        d_col_ptr, d_col_edge, pt, N, E, t0, rf);
+            }, algo == LDPC_ALGO_MSA, pc, inplace));
+        } else {
+            LAUNCH_ON(s, K_VAR, {
+                const bool in_regs = dispatch(vb, VarBuckets{}, [&](auto D, auto MSA) {
+                    klaunch(k_var_gr<MSA(), D()>, grid, blk, 0, s, scratch, v2c, prior, hard, active, d_col_ptr,
+                            d_col_edge, pt, N, E, t0);
+                }, !bp);
+                if (!in_regs && bp) klaunch(k_var_bp_gen, grid, blk, 0, s, scratch, v2c, prior, hard, active, d_col_ptr, d_col_edge, pt, N, E, t0);
+                else if (!in_regs) klaunch(k_var_msa_gen, grid, blk, 0, s, scratch, v2c, prior, hard, active, d_col_ptr, d_col_edge, pt, N, E, t0);
+            });
+        }
     }
-    if (algo == LDPC_ALGO_BP)
-        LAUNCH_ON(s, K_VAR, klaunch(k_var_bp_gen, grid, blk, 0, s, scratch, v2c, prior, hard, active, d_col_ptr, d_col_edge, pt, N, E, t0));
-    else
-        LAUNCH_ON(s, K_VAR, klaunch(k_var_msa_gen, grid, blk, 0, s, scratch, v2c, prior, hard, active, d_col_ptr, d_col_edge, pt, N, E, t0));
+    if (!ok) { set_error("variable phase: no kernel for these columns per wave"); return LDPC_ERR_ARG; }
     return LDPC_OK;
 }
 

@@ -950,6 +950,23 @@ __global__ __launch_bounds__(256) void k_var_m(typename Msg<INPLACE>::in c2v, ty
                                                  xcd_block(blockIdx.x, gridDim.x), rf);
 }
 
+// Closing block of the generic variable kernels: the ballot of the wave's
+// hard decisions h for one column, merged by lane 0 into its word hard[o]
+// under `mask` (the lanes decided in this step; the other lanes' bits stay).
+// o = t * N + j is formed inside the lane-0 branch: formed by the caller it
+// moved the fixed-pass variable kernels' scalar code (2-3 % per launch,
+// profiles/r11/generic_refactor).
+__device__ __forceinline__ void merge_hard(uint64_t* __restrict__ hard, int64_t t, int32_t N, int32_t j, uint64_t mask,
+                                           bool h, int lane)
+{
+    const uint64_t m = __ballot(h);
+    if (lane == 0 && mask) {
+        const size_t o = (size_t)t * N + j;
+        const uint64_t old = (mask == ~0ull) ? 0ull : hard[o];
+        hard[o] = (old & ~mask) | (m & mask);
+    }
+}
+
 // Generic column degree: the partial products go through the v2c array
 // exactly as the reference keeps them in e->pr.
 __global__ __launch_bounds__(256) void k_var_bp_gen(const double* __restrict__ lr, double* __restrict__ dmsg,
@@ -989,12 +1006,7 @@ __global__ __launch_bounds__(256) void k_var_bp_gen(const double* __restrict__ l
             dmsg[o] = 1.0 - 2.0 / (1.0 + v);
         }
     }
-    const uint64_t m = __ballot(h);
-    if (lane == 0) {
-        const size_t o = (size_t)t * N + j;
-        const uint64_t old = (act == ~0ull) ? 0ull : hard[o];
-        hard[o] = (old & ~act) | (m & act);
-    }
+    merge_hard(hard, t, N, j, act, h, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -1008,6 +1020,43 @@ __global__ __launch_bounds__(256) void k_var_bp_gen(const double* __restrict__ l
 // (x >= 0 ? +1 : -1) (NaN counts -1).  c2v = (double)sign * mag.
 // dc == 1: mag stays -1 -> 0, sign 1 -> 0.0 (dec.cpp:1427-1430).
 // ---------------------------------------------------------------------------
+// The rule for a row of degree 2 <= d <= D held in registers (x[k], k < d),
+// the results stored to dst[k * TILE]; the callers handle d < 2.
+template <int D, bool INPLACE = false>
+__device__ __forceinline__ void check_msa_compute_rt(const double (&x)[D], int32_t d, typename Msg<INPLACE>::out dst)
+{
+    double m1 = __builtin_inf(), m2 = __builtin_inf();
+    int32_t i1 = -1;
+    uint32_t neg = 0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        if (k < d) {
+            const double av = __builtin_fabs(x[k]);
+            neg ^= (x[k] >= 0) ? 0u : 1u;
+            if (av < m1) { m1 = av; i1 = k; }  // NaN never compares less; first index kept
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        if (k < d) {
+            const double av = __builtin_fabs(x[k]);
+            if (k != i1 && av < m2) m2 = av;
+        }
+    }
+    const double a0 = __builtin_fabs(x[0]), a1 = __builtin_fabs(x[1]);
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        if (k < d) {
+            const double af = (k == 0) ? a1 : a0;
+            double mag = (k == i1) ? m2 : m1;
+            if (__builtin_isnan(af)) mag = af;
+            const uint32_t nk = (x[k] >= 0) ? 0u : 1u;
+            const int sign = ((neg ^ nk) & 1u) ? -1 : 1;
+            dst[(size_t)k * TILE] = (double)sign * mag;
+        }
+    }
+}
+
 template <int DC, bool NT, bool INPLACE>
 __device__ __forceinline__ void check_msa_row(typename Msg<INPLACE>::in src, typename Msg<INPLACE>::out dst)
 {
@@ -1152,12 +1201,7 @@ __global__ __launch_bounds__(256) void k_var_msa_gen(const double* __restrict__ 
         h = !(L > 0);
         if (post) post[pj] = L;
     }
-    const uint64_t m = __ballot(h);
-    if (lane == 0) {
-        const size_t o = (size_t)t * N + j;
-        const uint64_t old = (act == ~0ull) ? 0ull : hard[o];
-        hard[o] = (old & ~act) | (m & act);
-    }
+    merge_hard(hard, t, N, j, act, h, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -1166,8 +1210,13 @@ __global__ __launch_bounds__(256) void k_var_msa_gen(const double* __restrict__ 
 // VGPRs: one load and one store per edge, where the *_gen kernels above take
 // their partial products through memory (about 40 B per edge per phase
 // instead of 16).  D is the engine's bucket for the graph's maximum degree
-// (engine.hip kGenBuckets); every loop runs the same operations in the same
-// order as the *_gen kernels (and the reference), guarded by k < d.
+// (engine.hip CheckBuckets / VarBuckets); every loop runs the same operations
+// in the same order as the *_gen kernels (and the reference), guarded by
+// k < d.  Each node update is stated once, as a helper on the register
+// array: check_bp_compute_rt, check_msa_compute_rt (above check_msa_row),
+// var_bp_update, var_msa_update, var_refill_init; the kernels (k_check_gr,
+// k_var_gr for fixed passes, k_check_gr_res, k_var_gr_cont for the lane
+// pools) differ in their lane masks and stores.
 template <int D, bool INPLACE = false>
 __device__ __forceinline__ void check_bp_compute_rt(const double (&x)[D], int32_t d, typename Msg<INPLACE>::out dst)
 {
@@ -1206,35 +1255,13 @@ __device__ __forceinline__ void check_bp_compute_rt(const double (&x)[D], int32_
     }
 }
 
-// BP check phase (dec.cpp:646-662), rows of degree <= D in registers
-template <int D>
-__global__ __launch_bounds__(256) void k_check_bp_gr(const double* __restrict__ dmsg, double* __restrict__ lr,
-                                                     const uint64_t* __restrict__ active,
-                                                     const int32_t* __restrict__ row_ptr, int32_t M, int64_t E,
-                                                     int64_t t0)
-{
-    const int lane = lane_id();
-    const int32_t row = blockIdx.x * 4 + wave_id();
-    const int64_t t = t0 + blockIdx.y;
-    if (row >= M) return;
-    if (!((active[t] >> lane) & 1ull)) return;
-    const int32_t a = row_ptr[row], d = row_ptr[row + 1] - a;
-    const double* src = dmsg + ((size_t)t * E + a) * TILE + lane;
-    double* dst = lr + ((size_t)blockIdx.y * E + a) * TILE + lane;
-    double x[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k)
-        if (k < d) x[k] = src[(size_t)k * TILE];
-    check_bp_compute_rt<D>(x, d, dst);
-}
-
-// min-sum check phase (dec.cpp:1398-1433, as k_check_msa_gen), rows of
-// degree <= D in registers
-template <int D>
-__global__ __launch_bounds__(256) void k_check_msa_gr(const double* __restrict__ v2c, double* __restrict__ c2v,
-                                                      const uint64_t* __restrict__ active,
-                                                      const int32_t* __restrict__ row_ptr, int32_t M, int64_t E,
-                                                      int64_t t0)
+// Check phase of a fixed pass, rows of degree <= D in registers: BP
+// (dec.cpp:646-662, check_bp_compute_rt) or min-sum (check_msa_compute_rt)
+template <bool MSA, int D>
+__global__ __launch_bounds__(256) void k_check_gr(const double* __restrict__ v2c, double* __restrict__ c2v,
+                                                  const uint64_t* __restrict__ active,
+                                                  const int32_t* __restrict__ row_ptr, int32_t M, int64_t E,
+                                                  int64_t t0)
 {
     const int lane = lane_id();
     const int32_t row = blockIdx.x * 4 + wave_id();
@@ -1243,54 +1270,108 @@ __global__ __launch_bounds__(256) void k_check_msa_gr(const double* __restrict__
     if (!((active[t] >> lane) & 1ull)) return;
     const int32_t a = row_ptr[row], d = row_ptr[row + 1] - a;
     double* dst = c2v + ((size_t)blockIdx.y * E + a) * TILE + lane;
-    if (d == 0) return;
-    if (d == 1) { dst[0] = 0.0; return; }
+    if constexpr (MSA) {
+        if (d == 0) return;
+        if (d == 1) { dst[0] = 0.0; return; }
+    }
     const double* src = v2c + ((size_t)t * E + a) * TILE + lane;
     double x[D];
 #pragma unroll
     for (int k = 0; k < D; ++k)
         if (k < d) x[k] = src[(size_t)k * TILE];
-    double m1 = __builtin_inf(), m2 = __builtin_inf();
-    int32_t i1 = -1;
-    uint32_t neg = 0;
+    if constexpr (MSA) check_msa_compute_rt<D>(x, d, dst);
+    else check_bp_compute_rt<D>(x, d, dst);
+}
+
+// BP column update (dec.cpp:667-693) of a column of degree d <= D in
+// registers: prior LR pv, incoming lr l[s] (s < d).
+//   forward  pr_s = P; P *= l_s (P starts at pv); P: NaN -> 1; h = (P <= 1)
+//   backward acc = 1; s = d-1..0: v = pr_s * acc; NaN -> 1; acc *= l_s;
+//            out(s, 1 - 2/(1+v)), the message of the next check phase
+// Yields the outgoing messages through out(s, value) as they are formed (a
+// fixed pass stores them, a lane pool keeps them for its whole-line stores),
+// the posterior ratio P into post[pj] (post may be null) and the decision h.
+template <int D, typename Out>
+__device__ __forceinline__ void var_bp_update(double pv, const double (&l)[D], int32_t d, double* __restrict__ post,
+                                              size_t pj, bool& h, Out&& out)
+{
+    double pr[D];
+    double p = pv;
 #pragma unroll
-    for (int k = 0; k < D; ++k) {
-        if (k < d) {
-            const double av = __builtin_fabs(x[k]);
-            neg ^= (x[k] >= 0) ? 0u : 1u;
-            if (av < m1) { m1 = av; i1 = k; }
-        }
-    }
+    for (int s = 0; s < D; ++s)
+        if (s < d) { pr[s] = p; p = p * l[s]; }
+    if (__builtin_isnan(p)) p = 1.0;
+    h = (p <= 1.0);
+    if (post) post[pj] = p;
+    double acc = 1.0;
 #pragma unroll
-    for (int k = 0; k < D; ++k) {
-        if (k < d) {
-            const double av = __builtin_fabs(x[k]);
-            if (k != i1 && av < m2) m2 = av;
-        }
-    }
-    const double a0 = __builtin_fabs(x[0]), a1 = __builtin_fabs(x[1]);
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        if (k < d) {
-            const double af = (k == 0) ? a1 : a0;
-            double mag = (k == i1) ? m2 : m1;
-            if (__builtin_isnan(af)) mag = af;
-            const uint32_t nk = (x[k] >= 0) ? 0u : 1u;
-            const int sign = ((neg ^ nk) & 1u) ? -1 : 1;
-            dst[(size_t)k * TILE] = (double)sign * mag;
+    for (int s = D - 1; s >= 0; --s) {
+        if (s < d) {
+            double v = pr[s] * acc;
+            if (__builtin_isnan(v)) v = 1.0;
+            acc = acc * l[s];
+            out(s, 1.0 - 2.0 / (1.0 + v));
         }
     }
 }
 
-// BP variable phase + decision (dec.cpp:667-693, as k_var_bp_gen), columns
-// of degree <= D in registers
-template <int D>
-__global__ __launch_bounds__(256) void k_var_bp_gr(const double* __restrict__ lr, double* __restrict__ dmsg,
-                                                   const double* __restrict__ prior, uint64_t* __restrict__ hard,
-                                                   const uint64_t* __restrict__ active,
-                                                   const int32_t* __restrict__ col_ptr,
-                                                   const int32_t* __restrict__ col_edge, double* __restrict__ post,
-                                                   int32_t N, int64_t E, int64_t t0)
+// Min-sum column update (Variable_Update_MSA_INF dec.cpp:1597-1619 +
+// Decision_MSA_INF dec.cpp:1659-1678), as var_bp_update: prior LLR pv,
+// incoming c2v l[s].  out(s, ((pv + l_0) + l_1) ... skipping l_s), ascending
+// row order; L = pv + l_0 + ... + l_{d-1} into post[pj]; h = !(L > 0).
+template <int D, typename Out>
+__device__ __forceinline__ void var_msa_update(double pv, const double (&l)[D], int32_t d, double* __restrict__ post,
+                                               size_t pj, bool& h, Out&& out)
+{
+#pragma unroll
+    for (int s = 0; s < D; ++s) {
+        if (s < d) {
+            double sum = pv;
+#pragma unroll
+            for (int r = 0; r < D; ++r)
+                if (r < d && r != s) sum = sum + l[r];
+            out(s, sum);
+        }
+    }
+    double L = pv;
+#pragma unroll
+    for (int s = 0; s < D; ++s)
+        if (s < d) L = L + l[s];
+    h = !(L > 0);
+    if (post) post[pj] = L;
+}
+
+// A refilled lane's Init_Belief_Propagation (dec.cpp:608-629) /
+// Init_MSA_INF (dec.cpp:1300-1329) from its input value x (exp_x: BP input
+// given as LLR): the lane's new prior np, every outgoing message and the
+// decision.
+template <bool MSA, int D>
+__device__ __forceinline__ void var_refill_init(double x, bool exp_x, double (&dv)[D], double& np, bool& h)
+{
+    if (MSA) {
+        np = x;
+#pragma unroll
+        for (int s = 0; s < D; ++s) dv[s] = x;
+        h = !(x > 0);
+    } else {
+        const double LR0 = exp_x ? exp(x) : x;
+        np = LR0;
+        const double d0 = 1.0 - 2.0 / (1.0 + LR0);
+#pragma unroll
+        for (int s = 0; s < D; ++s) dv[s] = d0;
+        h = (LR0 < 1.0);
+    }
+}
+
+// Variable phase + decision of a fixed pass, columns of degree <= D in
+// registers (var_bp_update / var_msa_update; as k_var_bp_gen / k_var_msa_gen)
+template <bool MSA, int D>
+__global__ __launch_bounds__(256) void k_var_gr(const double* __restrict__ c2v, double* __restrict__ v2c,
+                                                const double* __restrict__ prior, uint64_t* __restrict__ hard,
+                                                const uint64_t* __restrict__ active,
+                                                const int32_t* __restrict__ col_ptr,
+                                                const int32_t* __restrict__ col_edge, double* __restrict__ post,
+                                                int32_t N, int64_t E, int64_t t0)
 {
     const int lane = lane_id();
     const int32_t j = blockIdx.x * 4 + wave_id();
@@ -1304,99 +1385,25 @@ __global__ __launch_bounds__(256) void k_var_bp_gr(const double* __restrict__ lr
     bool h = false;
     if (live) {
         int32_t eid[D];
-        double l[D], pr[D];
+        double l[D];
 #pragma unroll
         for (int s = 0; s < D; ++s)
             if (s < d) eid[s] = col_edge[a + s];
 #pragma unroll
         for (int s = 0; s < D; ++s)
-            if (s < d) l[s] = lr[(tl + eid[s]) * TILE + lane];
+            if (s < d) l[s] = c2v[(tl + eid[s]) * TILE + lane];
         const size_t pj = ((size_t)t * N + j) * TILE + lane;
-        double p = prior[pj];
-#pragma unroll
-        for (int s = 0; s < D; ++s)
-            if (s < d) { pr[s] = p; p = p * l[s]; }
-        if (__builtin_isnan(p)) p = 1.0;
-        h = (p <= 1.0);
-        if (post) post[pj] = p;
-        double acc = 1.0;
-#pragma unroll
-        for (int s = D - 1; s >= 0; --s) {
-            if (s < d) {
-                double v = pr[s] * acc;
-                if (__builtin_isnan(v)) v = 1.0;
-                acc = acc * l[s];
-                dmsg[(tb + eid[s]) * TILE + lane] = 1.0 - 2.0 / (1.0 + v);
-            }
-        }
+        const double pv = prior[pj];
+        const auto store = [=](int s, double v) { v2c[(tb + eid[s]) * TILE + lane] = v; };
+        if constexpr (MSA) var_msa_update<D>(pv, l, d, post, pj, h, store);
+        else var_bp_update<D>(pv, l, d, post, pj, h, store);
     }
-    const uint64_t m = __ballot(h);
-    if (lane == 0) {
-        const size_t o = (size_t)t * N + j;
-        const uint64_t old = (act == ~0ull) ? 0ull : hard[o];
-        hard[o] = (old & ~act) | (m & act);
-    }
-}
-
-// min-sum variable phase + decision (dec.cpp:1597-1619, 1659-1678, as
-// k_var_msa_gen), columns of degree <= D in registers
-template <int D>
-__global__ __launch_bounds__(256) void k_var_msa_gr(const double* __restrict__ c2v, double* __restrict__ v2c,
-                                                    const double* __restrict__ prior, uint64_t* __restrict__ hard,
-                                                    const uint64_t* __restrict__ active,
-                                                    const int32_t* __restrict__ col_ptr,
-                                                    const int32_t* __restrict__ col_edge, double* __restrict__ post,
-                                                    int32_t N, int64_t E, int64_t t0)
-{
-    const int lane = lane_id();
-    const int32_t j = blockIdx.x * 4 + wave_id();
-    const int64_t t = t0 + blockIdx.y;
-    if (j >= N) return;
-    const uint64_t act = active[t];
-    if (act == 0) return;
-    const bool live = (act >> lane) & 1ull;
-    const int32_t a = col_ptr[j], d = col_ptr[j + 1] - a;
-    const size_t tb = (size_t)t * E, tl = (size_t)blockIdx.y * E;
-    bool h = false;
-    if (live) {
-        int32_t eid[D];
-        double c[D];
-#pragma unroll
-        for (int s = 0; s < D; ++s)
-            if (s < d) eid[s] = col_edge[a + s];
-#pragma unroll
-        for (int s = 0; s < D; ++s)
-            if (s < d) c[s] = c2v[(tl + eid[s]) * TILE + lane];
-        const size_t pj = ((size_t)t * N + j) * TILE + lane;
-        const double llr = prior[pj];
-#pragma unroll
-        for (int s = 0; s < D; ++s) {
-            if (s < d) {
-                double sum = llr;
-#pragma unroll
-                for (int r = 0; r < D; ++r)
-                    if (r < d && r != s) sum = sum + c[r];
-                v2c[(tb + eid[s]) * TILE + lane] = sum;
-            }
-        }
-        double L = llr;
-#pragma unroll
-        for (int s = 0; s < D; ++s)
-            if (s < d) L = L + c[s];
-        h = !(L > 0);
-        if (post) post[pj] = L;
-    }
-    const uint64_t m = __ballot(h);
-    if (lane == 0) {
-        const size_t o = (size_t)t * N + j;
-        const uint64_t old = (act == ~0ull) ? 0ull : hard[o];
-        hard[o] = (old & ~act) | (m & act);
-    }
+    merge_hard(hard, t, N, j, act, h, lane);
 }
 
 // Resident pool for row degrees <= D (codes other than the (8, 72)-regular
-// one): k_check_bp_gr / k_check_msa_gr in place over the pool tile
-// blockIdx.y, plus the fused syndrome of the previous variable phase (the
+// one): k_check_gr in place over the pool tile blockIdx.y, plus the fused
+// syndrome of the previous variable phase (the
 // row's parity over its ballots, CSR row_ptr / col_idx) and the tile's lane
 // bookkeeping by its last block (res_arrive), as k_check_bp<72, ., true>.
 // Every lane of an occupied 16-lane line runs (whole-line stores); no early
@@ -1440,6 +1447,9 @@ __global__ __launch_bounds__(256) void k_check_gr_res(double* msg, const int32_t
             for (int k = 0; k < D; ++k)
                 if (k < d) x[k] = p[(size_t)k * TILE];
             if constexpr (MSA) {
+                // check_msa_compute_rt's text, not a call of it: through the helper
+                // k_check_gr_res<true, 32> gets a 36-byte stack frame (a dead SGPR
+                // spill slot), whichever way the helper is cut
                 double m1 = __builtin_inf(), m2 = __builtin_inf();
                 int32_t i1 = -1;
                 uint32_t neg = 0;
@@ -1482,8 +1492,8 @@ __global__ __launch_bounds__(256) void k_check_gr_res(double* msg, const int32_t
 // (8, 72)-regular one; INPLACE: the resident pool, v2c == c2v, every load of
 // the column's edges ahead of its first store): var_m_block's lane handling -- finished lanes' outputs
 // first, refilled lanes' Init_Belief_Propagation (dec.cpp:608-629) /
-// Init_MSA_INF (dec.cpp:1300-1329), live lanes' update as k_var_bp_gr /
-// k_var_msa_gr -- for one column per wave with the degree read from col_ptr.
+// Init_MSA_INF (dec.cpp:1300-1329) (var_refill_init), live lanes' update as
+// k_var_gr -- for one column per wave with the degree read from col_ptr.
 // PC: coded priors (Refill::pcode / ptab, refills from Refill::in_code).
 template <bool MSA, int D, bool PC, bool INPLACE = false>
 __global__ __launch_bounds__(256) void k_var_gr_cont(typename Msg<INPLACE>::in c2v, typename Msg<INPLACE>::out v2c,
@@ -1559,58 +1569,11 @@ __global__ __launch_bounds__(256) void k_var_gr_cont(typename Msg<INPLACE>::in c
     for (int s = 0; s < D; ++s) dv[s] = 0.0;
     double np = live ? pv : 0.0;
     if (fr) {
-        const double x = xin;
-        if (MSA) {
-            np = x;
-#pragma unroll
-            for (int s = 0; s < D; ++s) dv[s] = x;
-            h = !(x > 0);
-        } else {
-            const double LR0 = (!PC && rf.in_is_llr) ? exp(x) : x;
-            np = LR0;
-            const double d0 = 1.0 - 2.0 / (1.0 + LR0);
-#pragma unroll
-            for (int s = 0; s < D; ++s) dv[s] = d0;
-            h = (LR0 < 1.0);
-        }
+        var_refill_init<MSA, D>(xin, !PC && rf.in_is_llr, dv, np, h);
     } else if (live) {
-        if (MSA) {
-#pragma unroll
-            for (int s = 0; s < D; ++s) {
-                if (s < d) {
-                    double sum = pv;
-#pragma unroll
-                    for (int r = 0; r < D; ++r)
-                        if (r < d && r != s) sum = sum + l[r];
-                    dv[s] = sum;
-                }
-            }
-            double L = pv;
-#pragma unroll
-            for (int s = 0; s < D; ++s)
-                if (s < d) L = L + l[s];
-            h = !(L > 0);
-            if (post) post[pj] = L;
-        } else {
-            double pr[D];
-            double p = pv;
-#pragma unroll
-            for (int s = 0; s < D; ++s)
-                if (s < d) { pr[s] = p; p = p * l[s]; }
-            if (__builtin_isnan(p)) p = 1.0;
-            h = (p <= 1.0);
-            if (post) post[pj] = p;
-            double acc = 1.0;
-#pragma unroll
-            for (int s = D - 1; s >= 0; --s) {
-                if (s < d) {
-                    double v = pr[s] * acc;
-                    if (__builtin_isnan(v)) v = 1.0;
-                    acc = acc * l[s];
-                    dv[s] = 1.0 - 2.0 / (1.0 + v);
-                }
-            }
-        }
+        const auto keep = [&](int s, double v) { dv[s] = v; };
+        if constexpr (MSA) var_msa_update<D>(pv, l, d, post, pj, h, keep);
+        else var_bp_update<D>(pv, l, d, post, pj, h, keep);
     }
     if (fr) {
         if constexpr (PC) rf.pcode[pj] = kin;
@@ -1622,12 +1585,7 @@ __global__ __launch_bounds__(256) void k_var_gr_cont(typename Msg<INPLACE>::in c
         for (int s = 0; s < D; ++s)
             if (s < d) v2c[(tb + eid[s]) * TILE + lane] = dv[s];
     }
-    const uint64_t m = __ballot(h);
-    if (lane == 0 && touched) {
-        const size_t o = (size_t)t * N + j;
-        const uint64_t old = (touched == ~0ull) ? 0ull : hard[o];
-        hard[o] = (old & ~touched) | (m & touched);
-    }
+    merge_hard(hard, t, N, j, touched, h, lane);
     if (fl && !fok) lane_fault(rf.fault, kFaultOutput, t * TILE + lane);
     asm volatile("" : "+v"(bad_v));
     if (bad_v) lane_fault(rf.fault, kFaultRefill, t * TILE + lane);

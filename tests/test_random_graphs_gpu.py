@@ -171,7 +171,7 @@ def _bucket_graph(rng, M, N, dc_max, dv_max):
     """Row 0 of degree dc_max, column 0 in dv_max rows, every other row of
     random degree 1..dc_max and no column in more than dv_max rows: the
     largest degrees sit exactly on (or one past) a register bucket of the
-    generic kernels (engine.hip kGenCheckBuckets / kGenVarBuckets)."""
+    generic kernels (engine.hip CheckBuckets / VarBuckets)."""
     sets = [set() for _ in range(M)]
     cnt = np.zeros(N, np.int64)
     for i in range(dv_max):
