@@ -319,19 +319,6 @@ __global__ void __launch_bounds__(256) k_strands_write(const uint8_t* __restrict
     }
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <class T> T* as() { return static_cast<T*>(p); }
-};
-
-int dev_copy_in(DevBuf& d, const void* src, size_t bytes)
-{
-    LDPC_HIP(hipMalloc(&d.p, std::max<size_t>(bytes, 16)));
-    if (bytes) LDPC_HIP(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-    return LDPC_OK;
-}
-
 // k_edit_distance on device-resident buffers (the host-buffer entry point, the
 // aligner's centres and the read planner): d_dist[p] for pairs whose indices
 // the caller has checked, lengths <= max_len <= 800.
@@ -362,82 +349,7 @@ int launch_dna_llr(const int32_t* d_kind, const int64_t* d_row_ptr, const uint8_
 
 using ldpc::set_error;
 
-static int dna_llr(int32_t n_strands, const int32_t* kind, const int64_t* row_ptr, const uint8_t* rows,
-                   const int32_t* row_q, int32_t payload_nt, double llr_unit, double* llr, uint8_t* int_mask,
-                   int8_t* codes, int32_t* codes_exact, int32_t device)
-{
-    using namespace ldpc;
-    if (n_strands < 0 || payload_nt < 1 || !kind || !row_ptr || !llr || (codes && !codes_exact)) {
-        set_error("ldpc_dna_llr: bad arguments");
-        return LDPC_ERR_ARG;
-    }
-    if (codes_exact) *codes_exact = 1;
-    if (n_strands == 0) return LDPC_OK;
-    const int64_t R = row_ptr[n_strands];
-    if (R < 0 || R > INT64_MAX / payload_nt || row_ptr[0] != 0 || (R > 0 && (!rows || !row_q))) {
-        set_error("ldpc_dna_llr: bad row_ptr / rows");
-        return LDPC_ERR_ARG;
-    }
-    for (int32_t s = 0; s < n_strands; s++) {
-        if (row_ptr[s + 1] < row_ptr[s] || kind[s] < 0 || kind[s] > 3) {
-            set_error("ldpc_dna_llr: row_ptr not monotone or kind out of range");
-            return LDPC_ERR_ARG;
-        }
-    }
-    int ndev = 0;
-    LDPC_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) {
-        set_error("ldpc_dna_llr: no such device");
-        return LDPC_ERR_DEVICE;
-    }
-    LDPC_HIP(hipSetDevice(device));
-    const size_t out_n = (size_t)2 * payload_nt * n_strands;
-    DevBuf dk, dp, dr, dq, dl, dm, dc, dov;
-    int rc;
-    if ((rc = dev_copy_in(dk, kind, sizeof(int32_t) * n_strands))) return rc;
-    if ((rc = dev_copy_in(dp, row_ptr, sizeof(int64_t) * ((size_t)n_strands + 1)))) return rc;
-    if ((rc = dev_copy_in(dr, rows, (size_t)R * payload_nt))) return rc;
-    if ((rc = dev_copy_in(dq, row_q, sizeof(int32_t) * (size_t)R))) return rc;
-    LDPC_HIP(hipMalloc(&dl.p, sizeof(double) * out_n));
-    if (int_mask) LDPC_HIP(hipMalloc(&dm.p, out_n));
-    if (codes) {
-        const int32_t zero = 0;
-        LDPC_HIP(hipMalloc(&dc.p, out_n));
-        if ((rc = dev_copy_in(dov, &zero, sizeof zero))) return rc;
-    }
-    if ((rc = launch_dna_llr(dk.as<int32_t>(), dp.as<int64_t>(), dr.as<uint8_t>(), dq.as<int32_t>(), n_strands,
-                             payload_nt, llr_unit, dl.as<double>(), int_mask ? dm.as<uint8_t>() : nullptr,
-                             codes ? dc.as<int8_t>() : nullptr, codes ? dov.as<int32_t>() : nullptr)))
-        return rc;
-    LDPC_HIP(hipMemcpy(llr, dl.p, sizeof(double) * out_n, hipMemcpyDeviceToHost));
-    if (int_mask) LDPC_HIP(hipMemcpy(int_mask, dm.p, out_n, hipMemcpyDeviceToHost));
-    if (codes) {
-        int32_t ov = 0;
-        LDPC_HIP(hipMemcpy(codes, dc.p, out_n, hipMemcpyDeviceToHost));
-        LDPC_HIP(hipMemcpy(&ov, dov.p, sizeof ov, hipMemcpyDeviceToHost));
-        *codes_exact = ov ? 0 : 1;
-    }
-    return LDPC_OK;
-}
-
-
 extern "C" {
-
-int ldpc_dna_llr(int32_t n_strands, const int32_t* kind, const int64_t* row_ptr, const uint8_t* rows,
-                 const int32_t* row_q, int32_t payload_nt, double llr_unit, double* llr, uint8_t* int_mask,
-                 int32_t device)
-{
-    return dna_llr(n_strands, kind, row_ptr, rows, row_q, payload_nt, llr_unit, llr, int_mask, nullptr, nullptr,
-                   device);
-}
-
-int ldpc_dna_llr_codes(int32_t n_strands, const int32_t* kind, const int64_t* row_ptr, const uint8_t* rows,
-                       const int32_t* row_q, int32_t payload_nt, double llr_unit, double* llr, uint8_t* int_mask,
-                       int8_t* codes, int32_t* codes_exact, int32_t device)
-{
-    return dna_llr(n_strands, kind, row_ptr, rows, row_q, payload_nt, llr_unit, llr, int_mask, codes, codes_exact,
-                   device);
-}
 
 int ldpc_dna_edit_distance(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, int64_t n_seqs,
                            const int32_t* pair_a, const int32_t* pair_b, int64_t n_pairs, int32_t* dist,
@@ -474,25 +386,21 @@ int ldpc_dna_edit_distance(const uint8_t* seqs, const int64_t* offsets, const in
         set_error("ldpc_dna_edit_distance: null sequences");
         return LDPC_ERR_ARG;
     }
-    int ndev = 0;
-    LDPC_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) {
-        set_error("ldpc_dna_edit_distance: no such device");
-        return LDPC_ERR_DEVICE;
-    }
-    LDPC_HIP(hipSetDevice(device));
-    DevBuf ds, doff, dlen, da, db, dd;
+    if (int rc = select_device("ldpc_dna_edit_distance", device)) return rc;
+    dev_ptr<uint8_t> ds;
+    dev_ptr<int64_t> doff;
+    dev_ptr<int32_t> dlen, da, db, dd;
     int rc;
-    if ((rc = dev_copy_in(ds, seqs, (size_t)total))) return rc;
-    if ((rc = dev_copy_in(doff, offsets, sizeof(int64_t) * (size_t)n_seqs))) return rc;
-    if ((rc = dev_copy_in(dlen, lengths, sizeof(int32_t) * (size_t)n_seqs))) return rc;
-    if ((rc = dev_copy_in(da, pair_a, sizeof(int32_t) * (size_t)n_pairs))) return rc;
-    if ((rc = dev_copy_in(db, pair_b, sizeof(int32_t) * (size_t)n_pairs))) return rc;
-    LDPC_HIP(hipMalloc(&dd.p, sizeof(int32_t) * (size_t)n_pairs));
-    if ((rc = launch_edit_distance(ds.as<uint8_t>(), doff.as<int64_t>(), dlen.as<int32_t>(), da.as<int32_t>(),
-                                   db.as<int32_t>(), n_pairs, max_len, dd.as<int32_t>())))
+    if ((rc = upload(ds, seqs, (size_t)total))) return rc;
+    if ((rc = upload(doff, offsets, (size_t)n_seqs))) return rc;
+    if ((rc = upload(dlen, lengths, (size_t)n_seqs))) return rc;
+    if ((rc = upload(da, pair_a, (size_t)n_pairs))) return rc;
+    if ((rc = upload(db, pair_b, (size_t)n_pairs))) return rc;
+    if ((rc = dev_alloc(dd, (size_t)n_pairs))) return rc;
+    if ((rc = launch_edit_distance(ds.get(), doff.get(), dlen.get(), da.get(),
+                                   db.get(), n_pairs, max_len, dd.get())))
         return rc;
-    LDPC_HIP(hipMemcpy(dist, dd.p, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    LDPC_HIP(hipMemcpy(dist, dd.get(), sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost));
     return LDPC_OK;
 }
 
@@ -562,24 +470,21 @@ int ldpc_dna_index_decode(const uint8_t* seqs, const int64_t* offsets, const int
         set_error("ldpc_dna_index_decode: too many reads for one call");
         return LDPC_ERR_UNSUPPORTED;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_error("ldpc_dna_index_decode: no such device");
-        return LDPC_ERR_DEVICE;
-    }
-    LDPC_HIP(hipSetDevice(device));
-    DevBuf ds, doff, dlen, di, dc;
+    if (int rc = select_device("ldpc_dna_index_decode", device)) return rc;
+    dev_ptr<uint8_t> ds;
+    dev_ptr<int64_t> doff;
+    dev_ptr<int32_t> dlen, di, dc;
     int rc;
-    if ((rc = dev_copy_in(ds, seqs, (size_t)total))) return rc;
-    if ((rc = dev_copy_in(doff, offsets, sizeof(int64_t) * (size_t)n))) return rc;
-    if ((rc = dev_copy_in(dlen, lengths, sizeof(int32_t) * (size_t)n))) return rc;
-    LDPC_HIP(hipMalloc(&di.p, sizeof(int32_t) * (size_t)n));
-    LDPC_HIP(hipMalloc(&dc.p, sizeof(int32_t) * (size_t)n));
-    hipLaunchKernelGGL(k_rs_index_decode, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ds.as<uint8_t>(),
-                       doff.as<int64_t>(), dlen.as<int32_t>(), n, di.as<int32_t>(), dc.as<int32_t>());
+    if ((rc = upload(ds, seqs, (size_t)total))) return rc;
+    if ((rc = upload(doff, offsets, (size_t)n))) return rc;
+    if ((rc = upload(dlen, lengths, (size_t)n))) return rc;
+    if ((rc = dev_alloc(di, (size_t)n))) return rc;
+    if ((rc = dev_alloc(dc, (size_t)n))) return rc;
+    hipLaunchKernelGGL(k_rs_index_decode, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ds.get(),
+                       doff.get(), dlen.get(), n, di.get(), dc.get());
     LDPC_HIP(hipGetLastError());
-    LDPC_HIP(hipMemcpy(index, di.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-    LDPC_HIP(hipMemcpy(cnumerr, dc.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    LDPC_HIP(hipMemcpy(index, di.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    LDPC_HIP(hipMemcpy(cnumerr, dc.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
     return LDPC_OK;
 }
 
@@ -634,21 +539,17 @@ int ldpc_dna_strands(const uint8_t* codewords, int32_t n_cw, int64_t N, const in
         set_error("ldpc_dna_strands: shape too large for one call");
         return LDPC_ERR_UNSUPPORTED;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_error("ldpc_dna_strands: no such device");
-        return LDPC_ERR_DEVICE;
-    }
-    LDPC_HIP(hipSetDevice(device));
-    DevBuf dcw, di, dout;
+    if (int rc = select_device("ldpc_dna_strands", device)) return rc;
+    dev_ptr<uint8_t> dcw, dout;
+    dev_ptr<int32_t> di;
     int rc;
-    if ((rc = dev_copy_in(dcw, codewords, (size_t)n_cw * (size_t)N))) return rc;
-    if ((rc = dev_copy_in(di, index, sizeof(int32_t) * (size_t)N))) return rc;
-    LDPC_HIP(hipMalloc(&dout.p, (size_t)N * (size_t)L));
+    if ((rc = upload(dcw, codewords, (size_t)n_cw * (size_t)N))) return rc;
+    if ((rc = upload(di, index, (size_t)N))) return rc;
+    if ((rc = dev_alloc(dout, (size_t)N * (size_t)L))) return rc;
     hipLaunchKernelGGL(k_strands_write, dim3((unsigned)((N + kStrTile - 1) / kStrTile), (unsigned)chunks), dim3(256),
-                       0, 0, dcw.as<uint8_t>(), di.as<int32_t>(), n_cw, N, dout.as<uint8_t>());
+                       0, 0, dcw.get(), di.get(), n_cw, N, dout.get());
     LDPC_HIP(hipGetLastError());
-    LDPC_HIP(hipMemcpy(out, dout.p, (size_t)N * (size_t)L, hipMemcpyDeviceToHost));
+    LDPC_HIP(hipMemcpy(out, dout.get(), (size_t)N * (size_t)L, hipMemcpyDeviceToHost));
     return LDPC_OK;
 }
 
@@ -828,12 +729,7 @@ int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes
     StarScripts s;
     star_scripts_init(a, &s);
     if (a.n_groups == 0) return star_finish(who, a, s);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_error(who + ": no such device");
-        return LDPC_ERR_DEVICE;
-    }
-    LDPC_HIP(hipSetDevice(device));
+    if (int rc = select_device(who.c_str(), device)) return rc;
     const int64_t budget_words = (workspace_bytes ? workspace_bytes : kStarDefaultWs) / 4;
 
     // groups the device takes: two reads or more, none longer than kStarMaxLen
@@ -852,12 +748,14 @@ int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes
         }
         if (k > 2) n_dist_pairs += k * (k - 1) / 2;
     }
-    DevBuf ds, doff, dlen;
+    dev_ptr<uint8_t> ds;
+    dev_ptr<int64_t> doff;
+    dev_ptr<int32_t> dlen;
     int rc;
-    if (!dev_seqs && (rc = dev_copy_in(ds, a.seqs, (size_t)seq_bytes))) return rc;
-    const uint8_t* d_seqs = dev_seqs ? dev_seqs : ds.as<uint8_t>();
-    if ((rc = dev_copy_in(doff, a.offsets, sizeof(int64_t) * (size_t)a.n_seqs))) return rc;
-    if ((rc = dev_copy_in(dlen, a.lengths, sizeof(int32_t) * (size_t)a.n_seqs))) return rc;
+    if (!dev_seqs && (rc = upload(ds, a.seqs, (size_t)seq_bytes))) return rc;
+    const uint8_t* d_seqs = dev_seqs ? dev_seqs : ds.get();
+    if ((rc = upload(doff, a.offsets, (size_t)a.n_seqs))) return rc;
+    if ((rc = upload(dlen, a.lengths, (size_t)a.n_seqs))) return rc;
 
     // the centres: k_edit_distance on all in-group pairs (k = 2: the tie goes to read 0)
     if (n_dist_pairs > 0) {
@@ -872,14 +770,14 @@ int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes
                     pb[(size_t)np] = (int32_t)(g0 + y);
                 }
         }
-        DevBuf da, db, dd;
-        if ((rc = dev_copy_in(da, pa.data(), sizeof(int32_t) * (size_t)np))) return rc;
-        if ((rc = dev_copy_in(db, pb.data(), sizeof(int32_t) * (size_t)np))) return rc;
-        LDPC_HIP(hipMalloc(&dd.p, sizeof(int32_t) * (size_t)np));
-        if ((rc = launch_edit_distance(d_seqs, doff.as<int64_t>(), dlen.as<int32_t>(), da.as<int32_t>(),
-                                       db.as<int32_t>(), np, max_len, dd.as<int32_t>())))
+        dev_ptr<int32_t> da, db, dd;
+        if ((rc = upload(da, pa.data(), (size_t)np))) return rc;
+        if ((rc = upload(db, pb.data(), (size_t)np))) return rc;
+        if ((rc = dev_alloc(dd, (size_t)np))) return rc;
+        if ((rc = launch_edit_distance(d_seqs, doff.get(), dlen.get(), da.get(),
+                                       db.get(), np, max_len, dd.get())))
             return rc;
-        LDPC_HIP(hipMemcpy(d.data(), dd.p, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost));
+        LDPC_HIP(hipMemcpy(d.data(), dd.get(), sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost));
         np = 0;
         std::vector<int64_t> dm;
         for (int64_t g = 0; g < a.n_groups; g++) {
@@ -962,33 +860,36 @@ int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes
         }
         pass_first.push_back(NB);
         passes = (int64_t)pass_first.size() - 1;
-        DevBuf dpr, dpc, dbf, dbw, dbp, dao, dio, dws, dat, dcnt, dins, ddist;
-        if ((rc = dev_copy_in(dpr, pr.data(), sizeof(int32_t) * (size_t)P))) return rc;
-        if ((rc = dev_copy_in(dpc, pc.data(), sizeof(int32_t) * (size_t)P))) return rc;
-        if ((rc = dev_copy_in(dbf, blk_first.data(), sizeof(int64_t) * (size_t)(NB + 1)))) return rc;
-        if ((rc = dev_copy_in(dbw, blk_ws.data(), sizeof(int64_t) * (size_t)NB))) return rc;
-        if ((rc = dev_copy_in(dbp, blk_wpr.data(), sizeof(int32_t) * (size_t)NB))) return rc;
-        if ((rc = dev_copy_in(dao, at_off.data(), sizeof(int64_t) * (size_t)P))) return rc;
-        if ((rc = dev_copy_in(dio, ins_off.data(), sizeof(int64_t) * (size_t)P))) return rc;
-        LDPC_HIP(hipMalloc(&dws.p, std::max<size_t>(sizeof(uint32_t) * (size_t)ws_words, 16)));
-        LDPC_HIP(hipMalloc(&dat.p, std::max<size_t>((size_t)at_total, 16)));
-        LDPC_HIP(hipMalloc(&dcnt.p, sizeof(int32_t) * (size_t)(at_total + P)));
-        LDPC_HIP(hipMalloc(&dins.p, std::max<size_t>((size_t)ins_total, 16)));
-        LDPC_HIP(hipMalloc(&ddist.p, sizeof(int32_t) * (size_t)P));
+        dev_ptr<int32_t> dpr, dpc, dbp, dcnt, ddist;
+        dev_ptr<int64_t> dbf, dbw, dao, dio;
+        dev_ptr<uint32_t> dws;
+        dev_ptr<uint8_t> dat, dins;
+        if ((rc = upload(dpr, pr.data(), (size_t)P))) return rc;
+        if ((rc = upload(dpc, pc.data(), (size_t)P))) return rc;
+        if ((rc = upload(dbf, blk_first.data(), (size_t)(NB + 1)))) return rc;
+        if ((rc = upload(dbw, blk_ws.data(), (size_t)NB))) return rc;
+        if ((rc = upload(dbp, blk_wpr.data(), (size_t)NB))) return rc;
+        if ((rc = upload(dao, at_off.data(), (size_t)P))) return rc;
+        if ((rc = upload(dio, ins_off.data(), (size_t)P))) return rc;
+        if ((rc = dev_alloc(dws, (size_t)ws_words))) return rc;
+        if ((rc = dev_alloc(dat, (size_t)at_total))) return rc;
+        if ((rc = dev_alloc(dcnt, (size_t)(at_total + P)))) return rc;
+        if ((rc = dev_alloc(dins, (size_t)ins_total))) return rc;
+        if ((rc = dev_alloc(ddist, (size_t)P))) return rc;
         const size_t lds = (sizeof(uint16_t) * (size_t)(max_n + 1) + (size_t)max_n) * 64;
         for (int64_t q = 0; q < passes; q++) {
             const int64_t b0 = pass_first[(size_t)q], nb = pass_first[(size_t)q + 1] - b0;
             hipLaunchKernelGGL(k_star_align_pairs, dim3((unsigned)nb), dim3(64), lds, 0, d_seqs,
-                               doff.as<int64_t>(), dlen.as<int32_t>(), dpr.as<int32_t>(), dpc.as<int32_t>(),
-                               dbf.as<int64_t>(), dbw.as<int64_t>(), dbp.as<int32_t>(), dao.as<int64_t>(),
-                               dio.as<int64_t>(), b0, max_n, dws.as<uint32_t>(), dat.as<uint8_t>(), dcnt.as<int32_t>(),
-                               dins.as<uint8_t>(), ddist.as<int32_t>());
+                               doff.get(), dlen.get(), dpr.get(), dpc.get(),
+                               dbf.get(), dbw.get(), dbp.get(), dao.get(),
+                               dio.get(), b0, max_n, dws.get(), dat.get(), dcnt.get(),
+                               dins.get(), ddist.get());
             LDPC_HIP(hipGetLastError());
         }
-        if (at_total) LDPC_HIP(hipMemcpy(h_at.data(), dat.p, (size_t)at_total, hipMemcpyDeviceToHost));
-        LDPC_HIP(hipMemcpy(h_cnt.data(), dcnt.p, sizeof(int32_t) * (size_t)(at_total + P), hipMemcpyDeviceToHost));
-        if (ins_total) LDPC_HIP(hipMemcpy(h_ins.data(), dins.p, (size_t)ins_total, hipMemcpyDeviceToHost));
-        LDPC_HIP(hipMemcpy(h_dist.data(), ddist.p, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost));
+        if (at_total) LDPC_HIP(hipMemcpy(h_at.data(), dat.get(), (size_t)at_total, hipMemcpyDeviceToHost));
+        LDPC_HIP(hipMemcpy(h_cnt.data(), dcnt.get(), sizeof(int32_t) * (size_t)(at_total + P), hipMemcpyDeviceToHost));
+        if (ins_total) LDPC_HIP(hipMemcpy(h_ins.data(), dins.get(), (size_t)ins_total, hipMemcpyDeviceToHost));
+        LDPC_HIP(hipMemcpy(h_dist.data(), ddist.get(), sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost));
     }
     for (int64_t p = 0; p < P; p++) {
         const int64_t q = pr[(size_t)p], m = a.lengths[q], n = a.lengths[pc[(size_t)p]];
@@ -1065,6 +966,68 @@ ldpc::plan::Args plan_args(const uint8_t* seqs, const int64_t* offsets, const in
                             payload_nt, align, kind, row_ptr, rows, row_q, stats};
 }
 
+// k_dna_llr on a device-resident plan, and its outputs to the host.
+int llr_from_plan(const ldpc::PlanDev& pd, int32_t n_strands, int32_t payload_nt, double llr_unit, double* llr,
+                  uint8_t* int_mask, int8_t* codes, int32_t* codes_exact)
+{
+    using namespace ldpc;
+    const size_t out_n = (size_t)2 * payload_nt * n_strands;
+    dev_ptr<double> dl;
+    dev_ptr<uint8_t> dm;   // null unless int_mask
+    dev_ptr<int8_t> dc;    // null unless codes, with dov
+    dev_ptr<int32_t> dov;
+    const int32_t zero = 0;
+    int rc;
+    if ((rc = dev_alloc(dl, out_n)) || (int_mask && (rc = dev_alloc(dm, out_n))) ||
+        (codes && ((rc = dev_alloc(dc, out_n)) || (rc = upload(dov, &zero, 1)))))
+        return rc;
+    if ((rc = launch_dna_llr(pd.kind.get(), pd.row_ptr.get(), pd.rows.get(), pd.row_q.get(), n_strands, payload_nt,
+                             llr_unit, dl.get(), dm.get(), dc.get(), dov.get())))
+        return rc;
+    LDPC_HIP(hipMemcpy(llr, dl.get(), sizeof(double) * out_n, hipMemcpyDeviceToHost));
+    if (int_mask) LDPC_HIP(hipMemcpy(int_mask, dm.get(), out_n, hipMemcpyDeviceToHost));
+    if (codes) {
+        int32_t ov = 0;
+        LDPC_HIP(hipMemcpy(codes, dc.get(), out_n, hipMemcpyDeviceToHost));
+        LDPC_HIP(hipMemcpy(&ov, dov.get(), sizeof ov, hipMemcpyDeviceToHost));
+        *codes_exact = ov ? 0 : 1;
+    }
+    return LDPC_OK;
+}
+
+// the LLRs of a plan made on the host
+int dna_llr(int32_t n_strands, const int32_t* kind, const int64_t* row_ptr, const uint8_t* rows, const int32_t* row_q,
+            int32_t payload_nt, double llr_unit, double* llr, uint8_t* int_mask, int8_t* codes, int32_t* codes_exact,
+            int32_t device)
+{
+    using namespace ldpc;
+    if (n_strands < 0 || payload_nt < 1 || !kind || !row_ptr || !llr || (codes && !codes_exact)) {
+        set_error("ldpc_dna_llr: bad arguments");
+        return LDPC_ERR_ARG;
+    }
+    if (codes_exact) *codes_exact = 1;
+    if (n_strands == 0) return LDPC_OK;
+    const int64_t R = row_ptr[n_strands];
+    if (R < 0 || R > INT64_MAX / payload_nt || row_ptr[0] != 0 || (R > 0 && (!rows || !row_q))) {
+        set_error("ldpc_dna_llr: bad row_ptr / rows");
+        return LDPC_ERR_ARG;
+    }
+    for (int32_t s = 0; s < n_strands; s++) {
+        if (row_ptr[s + 1] < row_ptr[s] || kind[s] < 0 || kind[s] > 3) {
+            set_error("ldpc_dna_llr: row_ptr not monotone or kind out of range");
+            return LDPC_ERR_ARG;
+        }
+    }
+    int rc;
+    if ((rc = select_device("ldpc_dna_llr", device))) return rc;
+    PlanDev pd;
+    pd.R = R;
+    if ((rc = upload(pd.kind, kind, (size_t)n_strands)) || (rc = upload(pd.row_ptr, row_ptr, (size_t)n_strands + 1)) ||
+        (rc = upload(pd.rows, rows, (size_t)R * payload_nt)) || (rc = upload(pd.row_q, row_q, (size_t)R)))
+        return rc;
+    return llr_from_plan(pd, n_strands, payload_nt, llr_unit, llr, int_mask, codes, codes_exact);
+}
+
 int reads_llr(const ldpc::plan::Args& a, int32_t device, int64_t workspace_bytes, double llr_unit, double* llr,
               uint8_t* int_mask, int8_t* codes, int32_t* codes_exact)
 {
@@ -1078,35 +1041,28 @@ int reads_llr(const ldpc::plan::Args& a, int32_t device, int64_t workspace_bytes
     if (int rc = plan_device(who, a, false, device, workspace_bytes, &pd)) return rc;
     if (codes_exact) *codes_exact = 1;
     if (a.n_strands == 0) return LDPC_OK;
-    const size_t out_n = (size_t)2 * a.payload_nt * a.n_strands;
-    DevBuf dl, dm, dc, dov;
-    int rc;
-    LDPC_HIP(hipMalloc(&dl.p, sizeof(double) * out_n));
-    if (int_mask) LDPC_HIP(hipMalloc(&dm.p, out_n));
-    if (codes) {
-        const int32_t zero = 0;
-        LDPC_HIP(hipMalloc(&dc.p, out_n));
-        if ((rc = dev_copy_in(dov, &zero, sizeof zero))) return rc;
-    }
-    if ((rc = launch_dna_llr(pd.kind.as<int32_t>(), pd.row_ptr.as<int64_t>(), pd.rows.as<uint8_t>(),
-                             pd.row_q.as<int32_t>(), a.n_strands, a.payload_nt, llr_unit, dl.as<double>(),
-                             int_mask ? dm.as<uint8_t>() : nullptr, codes ? dc.as<int8_t>() : nullptr,
-                             codes ? dov.as<int32_t>() : nullptr)))
-        return rc;
-    LDPC_HIP(hipMemcpy(llr, dl.p, sizeof(double) * out_n, hipMemcpyDeviceToHost));
-    if (int_mask) LDPC_HIP(hipMemcpy(int_mask, dm.p, out_n, hipMemcpyDeviceToHost));
-    if (codes) {
-        int32_t ov = 0;
-        LDPC_HIP(hipMemcpy(codes, dc.p, out_n, hipMemcpyDeviceToHost));
-        LDPC_HIP(hipMemcpy(&ov, dov.p, sizeof ov, hipMemcpyDeviceToHost));
-        *codes_exact = ov ? 0 : 1;
-    }
-    return LDPC_OK;
+    return llr_from_plan(pd, a.n_strands, a.payload_nt, llr_unit, llr, int_mask, codes, codes_exact);
 }
 
 }  // namespace
 
 extern "C" {
+
+int ldpc_dna_llr(int32_t n_strands, const int32_t* kind, const int64_t* row_ptr, const uint8_t* rows,
+                 const int32_t* row_q, int32_t payload_nt, double llr_unit, double* llr, uint8_t* int_mask,
+                 int32_t device)
+{
+    return dna_llr(n_strands, kind, row_ptr, rows, row_q, payload_nt, llr_unit, llr, int_mask, nullptr, nullptr,
+                   device);
+}
+
+int ldpc_dna_llr_codes(int32_t n_strands, const int32_t* kind, const int64_t* row_ptr, const uint8_t* rows,
+                       const int32_t* row_q, int32_t payload_nt, double llr_unit, double* llr, uint8_t* int_mask,
+                       int8_t* codes, int32_t* codes_exact, int32_t device)
+{
+    return dna_llr(n_strands, kind, row_ptr, rows, row_q, payload_nt, llr_unit, llr, int_mask, codes, codes_exact,
+                   device);
+}
 
 int ldpc_dna_plan_host(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, const int32_t* quals,
                        int64_t n_reads, const int32_t* index_vals, const int32_t* strands, int32_t n_strands,

@@ -372,7 +372,9 @@ unsigned plan_blocks(int64_t n, int per) { return (unsigned)std::max<int64_t>(1,
 
 // What stays on the device after the planner, for the fused call.
 struct PlanDev {
-    DevBuf kind, row_ptr, rows, row_q;
+    dev_ptr<int32_t> kind, row_q;
+    dev_ptr<int64_t> row_ptr;
+    dev_ptr<uint8_t> rows;
     int64_t R = 0;
 };
 
@@ -405,91 +407,88 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
         pd->R = 0;
         return LDPC_OK;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_error(who + ": no such device");
-        return LDPC_ERR_DEVICE;
-    }
-    LDPC_HIP(hipSetDevice(device));
+    if (int rc = select_device(who.c_str(), device)) return rc;
 
     const size_t nn = (size_t)std::max<int64_t>(n, 1), SS = (size_t)S;
-    DevBuf dseq, doff, dlen, dq, dstr, div, dne, dpos, dpoff, dplen, dcnt, dnotfull, dctl, dstart, dtmp, dids, dsoff,
-        dslen, dnp, drc, dpstart, dncand, dcptr;
+    dev_ptr<uint8_t> dseq;
+    dev_ptr<int64_t> doff, dpoff, dstart, dsoff, dnp, drc, dpstart, dncand, dcptr;
+    dev_ptr<int32_t> dlen, dq, dstr, div, dne, dpos, dplen, dcnt, dtmp, dids, dslen;
+    dev_ptr<PlanCtl> dctl;
     int rc;
-    if ((rc = dev_copy_in(dseq, a.seqs, (size_t)total))) return rc;
-    if ((rc = dev_copy_in(doff, a.offsets, sizeof(int64_t) * (size_t)n))) return rc;
-    if ((rc = dev_copy_in(dlen, a.lengths, sizeof(int32_t) * (size_t)n))) return rc;
-    if ((rc = dev_copy_in(dq, a.quals, sizeof(int32_t) * (size_t)n))) return rc;
-    if ((rc = dev_copy_in(dstr, a.strands, sizeof(int32_t) * SS))) return rc;
+    if ((rc = upload(dseq, a.seqs, (size_t)total))) return rc;
+    if ((rc = upload(doff, a.offsets, (size_t)n))) return rc;
+    if ((rc = upload(dlen, a.lengths, (size_t)n))) return rc;
+    if ((rc = upload(dq, a.quals, (size_t)n))) return rc;
+    if ((rc = upload(dstr, a.strands, SS))) return rc;
     PlanCtl ctl{};
     ctl.long_read = INT32_MAX;
     ctl.empty_strand = INT32_MAX;
-    if ((rc = dev_copy_in(dctl, &ctl, sizeof ctl))) return rc;
+    if ((rc = upload(dctl, &ctl, 1))) return rc;
     if (a.index_vals) {
-        if ((rc = dev_copy_in(div, a.index_vals, sizeof(int32_t) * (size_t)n))) return rc;
+        if ((rc = upload(div, a.index_vals, (size_t)n))) return rc;
     } else {
-        LDPC_HIP(hipMalloc(&div.p, sizeof(int32_t) * nn));
-        LDPC_HIP(hipMalloc(&dne.p, sizeof(int32_t) * nn));
+        if ((rc = dev_alloc(div, nn))) return rc;
+        if ((rc = dev_alloc(dne, nn))) return rc;
         if (n > 0) {
-            hipLaunchKernelGGL(k_rs_index_decode, dim3(plan_blocks(n, 256)), dim3(256), 0, 0, dseq.as<uint8_t>(),
-                               doff.as<int64_t>(), dlen.as<int32_t>(), n, div.as<int32_t>(), dne.as<int32_t>());
+            hipLaunchKernelGGL(k_rs_index_decode, dim3(plan_blocks(n, 256)), dim3(256), 0, 0, dseq.get(),
+                               doff.get(), dlen.get(), n, div.get(), dne.get());
             LDPC_HIP(hipGetLastError());
         }
     }
-    LDPC_HIP(hipMalloc(&dpos.p, sizeof(int32_t) * nn));
-    LDPC_HIP(hipMalloc(&dpoff.p, sizeof(int64_t) * nn));
-    LDPC_HIP(hipMalloc(&dplen.p, sizeof(int32_t) * nn));
-    LDPC_HIP(hipMalloc(&dtmp.p, sizeof(int32_t) * nn));
-    LDPC_HIP(hipMalloc(&dids.p, sizeof(int32_t) * nn));
-    LDPC_HIP(hipMalloc(&dsoff.p, sizeof(int64_t) * nn));
-    LDPC_HIP(hipMalloc(&dslen.p, sizeof(int32_t) * nn));
-    LDPC_HIP(hipMalloc(&dcnt.p, sizeof(int32_t) * SS * 3));  // counts, not-full flags, scatter cursors
-    LDPC_HIP(hipMemset(dcnt.p, 0, sizeof(int32_t) * SS * 3));
-    int32_t* d_cnt = dcnt.as<int32_t>();
+    if ((rc = dev_alloc(dpos, nn))) return rc;
+    if ((rc = dev_alloc(dpoff, nn))) return rc;
+    if ((rc = dev_alloc(dplen, nn))) return rc;
+    if ((rc = dev_alloc(dtmp, nn))) return rc;
+    if ((rc = dev_alloc(dids, nn))) return rc;
+    if ((rc = dev_alloc(dsoff, nn))) return rc;
+    if ((rc = dev_alloc(dslen, nn))) return rc;
+    if ((rc = dev_alloc(dcnt, SS * 3))) return rc;  // counts, not-full flags, scatter cursors
+    LDPC_HIP(hipMemset(dcnt.get(), 0, sizeof(int32_t) * SS * 3));
+    int32_t* d_cnt = dcnt.get();
     int32_t* d_notfull = d_cnt + SS;
     int32_t* d_cursor = d_cnt + 2 * SS;
-    LDPC_HIP(hipMalloc(&dstart.p, sizeof(int64_t) * (SS + 1)));
-    LDPC_HIP(hipMalloc(&dpstart.p, sizeof(int64_t) * (SS + 1)));
-    LDPC_HIP(hipMalloc(&dcptr.p, sizeof(int64_t) * (SS + 1)));
-    LDPC_HIP(hipMalloc(&pd->row_ptr.p, sizeof(int64_t) * (SS + 1)));
-    LDPC_HIP(hipMalloc(&dnp.p, sizeof(int64_t) * SS));
-    LDPC_HIP(hipMalloc(&drc.p, sizeof(int64_t) * SS));
-    LDPC_HIP(hipMalloc(&dncand.p, sizeof(int64_t) * SS));
-    LDPC_HIP(hipMalloc(&pd->kind.p, sizeof(int32_t) * SS));
-    PlanCtl* d_ctl = dctl.as<PlanCtl>();
+    if ((rc = dev_alloc(dstart, (SS + 1)))) return rc;
+    if ((rc = dev_alloc(dpstart, (SS + 1)))) return rc;
+    if ((rc = dev_alloc(dcptr, (SS + 1)))) return rc;
+    if ((rc = dev_alloc(pd->row_ptr, (SS + 1)))) return rc;
+    if ((rc = dev_alloc(dnp, SS))) return rc;
+    if ((rc = dev_alloc(drc, SS))) return rc;
+    if ((rc = dev_alloc(dncand, SS))) return rc;
+    if ((rc = dev_alloc(pd->kind, SS))) return rc;
+    PlanCtl* d_ctl = dctl.get();
     const dim3 b256(256), per_read(plan_blocks(n, 256)), per_strand(plan_blocks(S, 256));
 
     if (n > 0) {
-        hipLaunchKernelGGL(k_plan_locate, per_read, b256, 0, 0, div.as<int32_t>(),
-                           a.index_vals ? nullptr : dne.as<int32_t>(), doff.as<int64_t>(), dlen.as<int32_t>(), n,
-                           dstr.as<int32_t>(), S, nt, dpos.as<int32_t>(), dpoff.as<int64_t>(), dplen.as<int32_t>(),
+        hipLaunchKernelGGL(k_plan_locate, per_read, b256, 0, 0, div.get(),
+                           a.index_vals ? nullptr : dne.get(), doff.get(), dlen.get(), n,
+                           dstr.get(), S, nt, dpos.get(), dpoff.get(), dplen.get(),
                            d_cnt, d_notfull, d_ctl);
         LDPC_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_plan_scan<int32_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, d_cnt, (int64_t)S,
-                       dstart.as<int64_t>());
+                       dstart.get());
     LDPC_HIP(hipGetLastError());
     if (n > 0) {
-        hipLaunchKernelGGL(k_plan_place, per_read, b256, 0, 0, dpos.as<int32_t>(), n, S, dstart.as<int64_t>(), d_cursor,
-                           dtmp.as<int32_t>(), d_ctl);
+        hipLaunchKernelGGL(k_plan_place, per_read, b256, 0, 0, dpos.get(), n, S, dstart.get(), d_cursor,
+                           dtmp.get(), d_ctl);
         LDPC_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_plan_sort, dim3(plan_blocks((int64_t)S * 8, 256)), b256, 0, 0, dtmp.as<int32_t>(),
-                       dstart.as<int64_t>(), S, n, dpoff.as<int64_t>(), dplen.as<int32_t>(), dids.as<int32_t>(),
-                       dsoff.as<int64_t>(), dslen.as<int32_t>(), d_ctl);
+    hipLaunchKernelGGL(k_plan_sort, dim3(plan_blocks((int64_t)S * 8, 256)), b256, 0, 0, dtmp.get(),
+                       dstart.get(), S, n, dpoff.get(), dplen.get(), dids.get(),
+                       dsoff.get(), dslen.get(), d_ctl);
     LDPC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_plan_classify, per_strand, b256, 0, 0, dstart.as<int64_t>(), S, n, d_notfull,
-                       dids.as<int32_t>(), dslen.as<int32_t>(), dq.as<int32_t>(), nt, pd->kind.as<int32_t>(),
-                       dnp.as<int64_t>(), drc.as<int64_t>(), d_ctl);
+    hipLaunchKernelGGL(k_plan_classify, per_strand, b256, 0, 0, dstart.get(), S, n, d_notfull,
+                       dids.get(), dslen.get(), dq.get(), nt, pd->kind.get(),
+                       dnp.get(), drc.get(), d_ctl);
     LDPC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_plan_scan<int64_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, dnp.as<int64_t>(), (int64_t)S,
-                       dpstart.as<int64_t>());
+    hipLaunchKernelGGL(k_plan_scan<int64_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, dnp.get(), (int64_t)S,
+                       dpstart.get());
     LDPC_HIP(hipGetLastError());
 
     int64_t n_valid = 0, P = 0;
-    LDPC_HIP(hipMemcpy(&ctl, dctl.p, sizeof ctl, hipMemcpyDeviceToHost));
-    LDPC_HIP(hipMemcpy(&n_valid, dstart.as<int64_t>() + S, sizeof n_valid, hipMemcpyDeviceToHost));
-    LDPC_HIP(hipMemcpy(&P, dpstart.as<int64_t>() + S, sizeof P, hipMemcpyDeviceToHost));
+    LDPC_HIP(hipMemcpy(&ctl, dctl.get(), sizeof ctl, hipMemcpyDeviceToHost));
+    LDPC_HIP(hipMemcpy(&n_valid, dstart.get() + S, sizeof n_valid, hipMemcpyDeviceToHost));
+    LDPC_HIP(hipMemcpy(&P, dpstart.get() + S, sizeof P, hipMemcpyDeviceToHost));
     if (ctl.bad || n_valid < 0 || n_valid > n || P < 0) {
         set_error(who + ": the device plan is inconsistent");
         return LDPC_ERR_DEVICE;
@@ -510,35 +509,36 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
     }
 
     // distances, close reads, candidates
-    DevBuf dpa, dpb, ddist, dclose, dcand, darows, dwidth;
-    LDPC_HIP(hipMalloc(&dclose.p, (size_t)std::max<int64_t>(n_valid, 16)));
-    LDPC_HIP(hipMemset(dclose.p, 0, (size_t)std::max<int64_t>(n_valid, 16)));
+    dev_ptr<int32_t> dpa, dpb, ddist, dcand, dwidth;
+    dev_ptr<uint8_t> dclose, darows;
+    if ((rc = dev_alloc(dclose, (size_t)std::max<int64_t>(n_valid, 16)))) return rc;
+    LDPC_HIP(hipMemset(dclose.get(), 0, (size_t)std::max<int64_t>(n_valid, 16)));
     if (P > 0) {
-        LDPC_HIP(hipMalloc(&dpa.p, sizeof(int32_t) * (size_t)P));
-        LDPC_HIP(hipMalloc(&dpb.p, sizeof(int32_t) * (size_t)P));
-        LDPC_HIP(hipMalloc(&ddist.p, sizeof(int32_t) * (size_t)P));
-        hipLaunchKernelGGL(k_plan_pairs, dim3(plan_blocks(P, 256)), b256, 0, 0, dpstart.as<int64_t>(),
-                           dstart.as<int64_t>(), S, n_valid, P, dpa.as<int32_t>(), dpb.as<int32_t>(), d_ctl);
+        if ((rc = dev_alloc(dpa, (size_t)P))) return rc;
+        if ((rc = dev_alloc(dpb, (size_t)P))) return rc;
+        if ((rc = dev_alloc(ddist, (size_t)P))) return rc;
+        hipLaunchKernelGGL(k_plan_pairs, dim3(plan_blocks(P, 256)), b256, 0, 0, dpstart.get(),
+                           dstart.get(), S, n_valid, P, dpa.get(), dpb.get(), d_ctl);
         LDPC_HIP(hipGetLastError());
-        if ((rc = launch_edit_distance(dseq.as<uint8_t>(), dsoff.as<int64_t>(), dslen.as<int32_t>(), dpa.as<int32_t>(),
-                                       dpb.as<int32_t>(), P, std::max(ctl.max_ragged_len, 0), ddist.as<int32_t>())))
+        if ((rc = launch_edit_distance(dseq.get(), dsoff.get(), dslen.get(), dpa.get(),
+                                       dpb.get(), P, std::max(ctl.max_ragged_len, 0), ddist.get())))
             return rc;
-        hipLaunchKernelGGL(k_plan_close, dim3(plan_blocks(P, 256)), b256, 0, 0, dpa.as<int32_t>(), dpb.as<int32_t>(),
-                           ddist.as<int32_t>(), P, n_valid, dclose.as<uint8_t>(), d_ctl);
+        hipLaunchKernelGGL(k_plan_close, dim3(plan_blocks(P, 256)), b256, 0, 0, dpa.get(), dpb.get(),
+                           ddist.get(), P, n_valid, dclose.get(), d_ctl);
         LDPC_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_plan_cand_count, per_strand, b256, 0, 0, dstart.as<int64_t>(), S, n_valid, dnp.as<int64_t>(),
-                       dclose.as<uint8_t>(), dncand.as<int64_t>(), drc.as<int64_t>());
+    hipLaunchKernelGGL(k_plan_cand_count, per_strand, b256, 0, 0, dstart.get(), S, n_valid, dnp.get(),
+                       dclose.get(), dncand.get(), drc.get());
     LDPC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_plan_scan<int64_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, dncand.as<int64_t>(), (int64_t)S,
-                       dcptr.as<int64_t>());
+    hipLaunchKernelGGL(k_plan_scan<int64_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, dncand.get(), (int64_t)S,
+                       dcptr.get());
     LDPC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_plan_scan<int64_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, drc.as<int64_t>(), (int64_t)S,
-                       pd->row_ptr.as<int64_t>());
+    hipLaunchKernelGGL(k_plan_scan<int64_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, drc.get(), (int64_t)S,
+                       pd->row_ptr.get());
     LDPC_HIP(hipGetLastError());
     int64_t C = 0, R = 0;
-    LDPC_HIP(hipMemcpy(&C, dcptr.as<int64_t>() + S, sizeof C, hipMemcpyDeviceToHost));
-    LDPC_HIP(hipMemcpy(&R, pd->row_ptr.as<int64_t>() + S, sizeof R, hipMemcpyDeviceToHost));
+    LDPC_HIP(hipMemcpy(&C, dcptr.get() + S, sizeof C, hipMemcpyDeviceToHost));
+    LDPC_HIP(hipMemcpy(&R, pd->row_ptr.get() + S, sizeof R, hipMemcpyDeviceToHost));
     if (C < 0 || C > n_valid || R < 0 || R > n_valid) {
         set_error(who + ": the device plan is inconsistent");
         return LDPC_ERR_DEVICE;
@@ -547,20 +547,20 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
     // the aligner: group s = the candidates of strand s (empty for most strands)
     int64_t n_aligned = 0;
     std::vector<int32_t> width((size_t)S, 0);
-    LDPC_HIP(hipMalloc(&dcand.p, sizeof(int32_t) * (size_t)std::max<int64_t>(C, 4)));
+    if ((rc = dev_alloc(dcand, (size_t)C))) return rc;
     if (C > 0) {
         if (!a.align) {
             set_error(who + ": ragged strands need an aligner (align = 0)");
             return LDPC_ERR_ARG;
         }
-        hipLaunchKernelGGL(k_plan_cand_fill, per_strand, b256, 0, 0, dstart.as<int64_t>(), S, n_valid,
-                           dcptr.as<int64_t>(), C, dclose.as<uint8_t>(), dids.as<int32_t>(), dcand.as<int32_t>(), d_ctl);
+        hipLaunchKernelGGL(k_plan_cand_fill, per_strand, b256, 0, 0, dstart.get(), S, n_valid,
+                           dcptr.get(), C, dclose.get(), dids.get(), dcand.get(), d_ctl);
         LDPC_HIP(hipGetLastError());
         std::vector<int64_t> cptr((size_t)S + 1), coff((size_t)C), out_ptr((size_t)S + 1);
         std::vector<int32_t> cand((size_t)C), clen((size_t)C), centre((size_t)S);
         std::vector<uint8_t> out;
-        LDPC_HIP(hipMemcpy(cptr.data(), dcptr.p, sizeof(int64_t) * (SS + 1), hipMemcpyDeviceToHost));
-        LDPC_HIP(hipMemcpy(cand.data(), dcand.p, sizeof(int32_t) * (size_t)C, hipMemcpyDeviceToHost));
+        LDPC_HIP(hipMemcpy(cptr.data(), dcptr.get(), sizeof(int64_t) * (SS + 1), hipMemcpyDeviceToHost));
+        LDPC_HIP(hipMemcpy(cand.data(), dcand.get(), sizeof(int32_t) * (size_t)C, hipMemcpyDeviceToHost));
         const int64_t skip = a.index_vals ? 0 : rs::kPrefixNt;
         if (cptr[0] != 0 || cptr[(size_t)S] != C) {
             set_error(who + ": the device plan is inconsistent");
@@ -578,7 +578,7 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
         StarCall sc{a.seqs, coff.data(), clen.data(), C, cptr.data(), (int64_t)S, centre.data(), width.data(),
                     out_ptr.data(), nullptr, 0, nullptr, nullptr};
         sc.out_vec = &out;
-        if ((rc = star_align_device(sc, device, workspace_bytes, nullptr, who, dseq.as<uint8_t>()))) return rc;
+        if ((rc = star_align_device(sc, device, workspace_bytes, nullptr, who, dseq.get()))) return rc;
         // the rows to upload: the aligned row (width == payload_nt), else its last byte in byte 0
         std::vector<uint8_t> arows((size_t)C * (size_t)nt, star::kGap);
         for (int32_t s = 0; s < S; s++) {
@@ -592,32 +592,32 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
                 else if (w > 0) dst[0] = row[w - 1];
             }
         }
-        if ((rc = dev_copy_in(darows, arows.data(), arows.size()))) return rc;
+        if ((rc = upload(darows, arows.data(), arows.size()))) return rc;
     }
-    if ((rc = dev_copy_in(dwidth, width.data(), sizeof(int32_t) * SS))) return rc;
+    if ((rc = upload(dwidth, width.data(), SS))) return rc;
 
-    LDPC_HIP(hipMalloc(&pd->rows.p, std::max<size_t>((size_t)R * (size_t)nt, 16)));
-    LDPC_HIP(hipMalloc(&pd->row_q.p, sizeof(int32_t) * (size_t)std::max<int64_t>(R, 4)));
+    if ((rc = dev_alloc(pd->rows, (size_t)R * (size_t)nt))) return rc;
+    if ((rc = dev_alloc(pd->row_q, (size_t)R))) return rc;
     if (R > 0) {
         hipLaunchKernelGGL(k_plan_rows, dim3((unsigned)std::min<int64_t>((R + 3) / 4, 2048)), b256, 0, 0,
-                           pd->row_ptr.as<int64_t>(), S, R, dstart.as<int64_t>(), n_valid, n, dcptr.as<int64_t>(), C,
-                           dcand.as<int32_t>(), darows.as<uint8_t>(), dwidth.as<int32_t>(), dseq.as<uint8_t>(),
-                           dsoff.as<int64_t>(), dslen.as<int32_t>(), dids.as<int32_t>(), dq.as<int32_t>(), nt,
-                           pd->kind.as<int32_t>(), pd->rows.as<uint8_t>(), pd->row_q.as<int32_t>(), d_ctl);
+                           pd->row_ptr.get(), S, R, dstart.get(), n_valid, n, dcptr.get(), C,
+                           dcand.get(), darows.get(), dwidth.get(), dseq.get(),
+                           dsoff.get(), dslen.get(), dids.get(), dq.get(), nt,
+                           pd->kind.get(), pd->rows.get(), pd->row_q.get(), d_ctl);
         LDPC_HIP(hipGetLastError());
     }
-    LDPC_HIP(hipMemcpy(&ctl, dctl.p, sizeof ctl, hipMemcpyDeviceToHost));
+    LDPC_HIP(hipMemcpy(&ctl, dctl.get(), sizeof ctl, hipMemcpyDeviceToHost));
     if (ctl.bad) {
         set_error(who + ": the device plan is inconsistent");
         return LDPC_ERR_DEVICE;
     }
     pd->R = R;
-    if (a.kind) LDPC_HIP(hipMemcpy(a.kind, pd->kind.p, sizeof(int32_t) * SS, hipMemcpyDeviceToHost));
+    if (a.kind) LDPC_HIP(hipMemcpy(a.kind, pd->kind.get(), sizeof(int32_t) * SS, hipMemcpyDeviceToHost));
     if (host_outputs) {
-        LDPC_HIP(hipMemcpy(a.row_ptr, pd->row_ptr.p, sizeof(int64_t) * (SS + 1), hipMemcpyDeviceToHost));
+        LDPC_HIP(hipMemcpy(a.row_ptr, pd->row_ptr.get(), sizeof(int64_t) * (SS + 1), hipMemcpyDeviceToHost));
         if (R > 0) {
-            LDPC_HIP(hipMemcpy(a.rows, pd->rows.p, (size_t)R * (size_t)nt, hipMemcpyDeviceToHost));
-            LDPC_HIP(hipMemcpy(a.row_q, pd->row_q.p, sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost));
+            LDPC_HIP(hipMemcpy(a.rows, pd->rows.get(), (size_t)R * (size_t)nt, hipMemcpyDeviceToHost));
+            LDPC_HIP(hipMemcpy(a.row_q, pd->row_q.get(), sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost));
         }
     }
     if (a.stats) {

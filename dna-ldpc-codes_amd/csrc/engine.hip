@@ -139,13 +139,14 @@ Engine::~Engine()
     if (stream) hipStreamDestroy(stream);
 }
 
+// the shared upload (hip_own.hpp) into one of the engine's raw members, which ~Engine frees
 template <typename T>
 static int upload(T** dst, const std::vector<T>& v)
 {
-    const size_t n = std::max<size_t>(v.size(), 1);
-    LDPC_HIP(hipMalloc((void**)dst, n * sizeof(T)));
-    if (!v.empty()) LDPC_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return LDPC_OK;
+    dev_ptr<T> p;
+    int rc = upload(p, v);
+    *dst = p.release();
+    return rc;
 }
 
 // MSA-C scratch of `tiles` group tiles: record planes [tiles][M][4][64] fp64
@@ -220,7 +221,7 @@ int Engine::init(const HostGraph* graph, int dev, int algorithm, int64_t chunk, 
     device = dev;
     algo = algorithm;
     if (resolved && schedule && (schedule->flags_set & kResolved)) {
-        sched = *schedule;  // the host API's slot: resolved once per call (capi.cpp)
+        sched = *schedule;  // the host API's slot: resolved once per call (host_decode.cpp)
         sched.pool_tiles = std::max(sched.pool_tiles, 0);
         sched.poll_every = std::max(sched.poll_every, 1);
         sched.syn_blocks = std::min(std::max(sched.syn_blocks, 1), 256);
@@ -229,10 +230,7 @@ int Engine::init(const HostGraph* graph, int dev, int algorithm, int64_t chunk, 
     }
     if (algo < LDPC_ALGO_BP || algo > LDPC_ALGO_GALLAGER_B2) { set_error("unknown algorithm"); return LDPC_ERR_ARG; }
     const bool int_algo = algo >= LDPC_ALGO_QMSA;
-    int ndev = 0;
-    LDPC_HIP(hipGetDeviceCount(&ndev));
-    if (dev < 0 || dev >= ndev) { set_error("device ordinal out of range"); return LDPC_ERR_DEVICE; }
-    LDPC_HIP(hipSetDevice(dev));
+    if (int rc = select_device("engine", dev)) return rc;
     LDPC_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
 
     const bool reg_72_8 = g->regular_dc && g->dc_max == 72 && g->regular_dv && g->dv_max == 8;
@@ -398,6 +396,25 @@ int32_t Engine::flags() const
 // kernel on the same buffer (no syndrome bookkeeping; timing only).
 int Engine::probe(int probes)
 {
+    // The engine's pool joins the candidates.  On every exit the best one --
+    // the engine's own unless a faster one was timed -- is the engine's pool
+    // again, the others are freed, and res / profile_stride are as they were.
+    std::vector<dev_ptr<double>> cand;
+    cand.emplace_back(res ? v2c : c2v);
+    size_t best = 0;
+    const int saved_stride = profile_stride;
+    const bool saved_res = res;
+    const int rc = time_candidates(probes, cand, &best);
+    res = saved_res;
+    profile_stride = saved_stride;
+    c2v = cand[best].release();
+    if (res) v2c = c2v;
+    for (int k = 0; k < K_NCLASS; k++) launches[k] = 0;
+    return rc;
+}
+
+int Engine::time_candidates(int probes, std::vector<dev_ptr<double>>& cand, size_t* best)
+{
     const size_t E = (size_t)std::max<int64_t>(g->E, 1);
     const size_t bytes = res ? (size_t)cap * E * sizeof(double) : c2v_bytes;
     const unsigned gt = (unsigned)(res ? cap_tiles : std::min<int64_t>(group_tiles, cap_tiles));
@@ -405,48 +422,34 @@ int Engine::probe(int probes)
     LDPC_HIP(hipMemsetAsync(prior, 0, (size_t)gt * 64 * g->N * sizeof(double), stream));
     LDPC_HIP(hipMemsetAsync(active, 0xff, (size_t)gt * sizeof(uint64_t), stream));
     if (d_sgn) LDPC_HIP(hipMemsetAsync(d_sgn, 0, (size_t)gt * 64 * g->N, stream));
-    std::vector<double*> cand{res ? v2c : c2v};
     for (int i = 1; i < probes; i++) {
-        double* p = nullptr;
-        if (hipMalloc((void**)&p, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-        cand.push_back(p);
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
+        cand.emplace_back(static_cast<double*>(p));
     }
-    for (double* p : cand) LDPC_HIP(hipMemsetAsync(p, 0, bytes, stream));
-    hipEvent_t e0, e1;
-    LDPC_HIP(hipEventCreate(&e0));
-    LDPC_HIP(hipEventCreate(&e1));
-    const int saved_stride = profile_stride;
+    for (auto& p : cand) LDPC_HIP(hipMemsetAsync(p.get(), 0, bytes, stream));
+    Event e0, e1;
+    int rc;
+    if ((rc = make_event(e0, hipEventDefault)) || (rc = make_event(e1, hipEventDefault))) return rc;
     profile_stride = 0;
-    const bool saved_res = res;
+    const bool in_place = res;
     res = false;  // plain check kernel (launch_check), in place when scratch == v2c
-    size_t best = 0;
     float best_ms = 1e30f;
-    int rc = LDPC_OK;
-    for (size_t c = 0; c < cand.size() && rc == LDPC_OK; c++) {
-        double* scratch = cand[c];
-        if (saved_res) v2c = c2v = cand[c];
-        for (int rep = 0; rep < 5 && rc == LDPC_OK; rep++) {  // rep 0 warms up
-            if (rep == 1 && hipEventRecord(e0, stream) != hipSuccess) rc = LDPC_ERR_DEVICE;
-            if (!rc) rc = launch_check(stream, scratch, 0, gt);
-            if (!rc) rc = launch_var(stream, scratch, 0, gt, nullptr, dev::Refill{});
+    for (size_t c = 0; c < cand.size(); c++) {
+        double* scratch = cand[c].get();
+        if (in_place) v2c = c2v = scratch;
+        for (int rep = 0; rep < 5; rep++) {  // rep 0 warms up
+            if (rep == 1) LDPC_HIP(hipEventRecord(e0.get(), stream));
+            if ((rc = launch_check(stream, scratch, 0, gt))) return rc;
+            if ((rc = launch_var(stream, scratch, 0, gt, nullptr, dev::Refill{}))) return rc;
         }
-        if (rc) break;
-        LDPC_HIP(hipEventRecord(e1, stream));
-        LDPC_HIP(hipEventSynchronize(e1));
+        LDPC_HIP(hipEventRecord(e1.get(), stream));
+        LDPC_HIP(hipEventSynchronize(e1.get()));
         float ms = 0;
-        LDPC_HIP(hipEventElapsedTime(&ms, e0, e1));
-        if (ms < best_ms) { best_ms = ms; best = c; }
+        LDPC_HIP(hipEventElapsedTime(&ms, e0.get(), e1.get()));
+        if (ms < best_ms) { best_ms = ms; *best = c; }
     }
-    res = saved_res;
-    profile_stride = saved_stride;
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    for (size_t c = 0; c < cand.size(); c++)
-        if (c != best) (void)hipFree(cand[c]);
-    if (res) v2c = c2v = cand[best];
-    else c2v = cand[best];
-    for (int k = 0; k < K_NCLASS; k++) launches[k] = 0;
-    return rc;
+    return LDPC_OK;
 }
 
 hipEvent_t Engine::get_event()

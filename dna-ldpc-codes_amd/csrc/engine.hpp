@@ -10,22 +10,10 @@
 
 #include "../../include/ldpc_amd.h"
 #include "graph.hpp"
+#include "hip_own.hpp"  // set_error, LDPC_HIP, the owning handles
 #include "kargs.hpp"
 
 namespace ldpc {
-
-// thread-local error string behind ldpc_last_error()
-void set_error(const std::string& msg);
-const char* last_error();
-
-#define LDPC_HIP(call)                                                                           \
-    do {                                                                                         \
-        hipError_t _e = (call);                                                                  \
-        if (_e != hipSuccess) {                                                                  \
-            ::ldpc::set_error(std::string(#call) + ": " + hipGetErrorString(_e));                \
-            return LDPC_ERR_DEVICE;                                                              \
-        }                                                                                        \
-    } while (0)
 
 enum KClass { K_CHECK = 0, K_VAR = 1, K_SYN = 2, K_INIT = 3, K_FINAL = 4, K_OTHER = 5, K_NCLASS = 6 };
 
@@ -180,6 +168,7 @@ struct Engine {
     int mark_begin(KClass c, hipStream_t s, hipEvent_t* b);
     int mark_end(KClass c, hipStream_t s, hipEvent_t b);
     int probe(int probes);
+    int time_candidates(int probes, std::vector<dev_ptr<double>>& cand, size_t* best);
     int launch_check(hipStream_t s, double* scratch, int64_t t0, unsigned gt);
     int launch_var(hipStream_t s, double* scratch, int64_t t0, unsigned gt, double* pt, const dev::Refill& rf);
     int var_cpw_for(const dev::Refill& rf) const;

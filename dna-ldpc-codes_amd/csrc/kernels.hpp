@@ -2103,13 +2103,13 @@ __global__ __launch_bounds__(256) void k_unpack_hard(const uint64_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------
-// Host-API input path (capi.cpp): LR = table[code + 127], the table holding
+// Host-API input path (host_decode.cpp): LR = table[code + 127], the table holding
 // the host libm's exp(k * unit) -- the reference's LR = exp(LLR)
 // (DNA_main.cpp:1344) for LLRs that are exact multiples k * unit, which the
 // host checked value by value.  8 codes per thread (one 8-byte load).
 // ---------------------------------------------------------------------------
 // hard bits u8 [n][8] -> one byte per 8 (bit r = byte r), for the host API's
-// D2H copy (capi.cpp unpacks them into the caller's one-byte-per-bit array)
+// D2H copy (host_decode.cpp unpacks them into the caller's one-byte-per-bit array)
 __global__ __launch_bounds__(256) void k_pack_bits(const uint64_t* __restrict__ in, uint8_t* __restrict__ out, int64_t n)
 {
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {

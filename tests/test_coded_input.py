@@ -119,7 +119,7 @@ def test_coded_lr_table_and_oracle(gpu, G, og, codewords):
 
 
 def test_host_api_min_sum_code_path(G, og, codewords):
-    """ldpc_decode sends lattice LLR batches as codes for min-sum too (capi.cpp
+    """ldpc_decode sends lattice LLR batches as codes for min-sum too (host_decode.cpp
     code table path): equal to the oracle and to the fp64 path (lr_table off)."""
     llr = synth.bsc_llrs(codewords, 0, 200, seed=2026, p=0.002)
     ref_h, ref_p, ref_it, ref_v = og.decode_batch(llr, 50, algo=1, post_mode=0, threads=8)

@@ -406,7 +406,7 @@ def test_split_syndrome_bitexact(gpu, og, codewords, algo, msa_c, group, chunk, 
 
 
 def test_host_lr_table_path(G, og, codewords):
-    """ldpc_decode's LR table path (capi.cpp): LLRs that are exact multiples
+    """ldpc_decode's LR table path (host_decode.cpp): LLRs that are exact multiples
     k * unit (the DNA alphabet) cross PCIe as one byte each and become
     table[k] = host exp(k * unit), the same bits as exp(LLR).  Bit-exact
     against the oracle (host exp), identical to the exp path (lr_table off),
