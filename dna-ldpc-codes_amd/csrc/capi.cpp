@@ -293,8 +293,8 @@ ldpc_engine* ldpc_engine_create(const ldpc_graph* g, int32_t device, int32_t alg
 int ldpc_engine_info(ldpc_engine* e, int64_t* cap, int64_t* group_tiles, int32_t* flags)
 {
     if (!e) { set_error("null engine"); return LDPC_ERR_ARG; }
-    if (cap) *cap = e->e->cap;
-    if (group_tiles) *group_tiles = e->e->group_tiles;
+    if (cap) *cap = e->e->p.cap;
+    if (group_tiles) *group_tiles = e->e->p.group_tiles;
     if (flags) *flags = e->e->flags();
     return LDPC_OK;
 }
@@ -323,7 +323,7 @@ int ldpc_engine_sync(ldpc_engine* e)
     return e->e->sync();
 }
 
-void* ldpc_engine_stream(ldpc_engine* e) { return e ? (void*)e->e->stream : nullptr; }
+void* ldpc_engine_stream(ldpc_engine* e) { return e ? (void*)e->e->stream.get() : nullptr; }
 
 int ldpc_engine_gen_bsc(ldpc_engine* e, double* d_out, int32_t out_kind, int64_t b0, int64_t B,
                         const uint8_t* d_codewords, int32_t n_cw, uint64_t seed, double p, double llr_mag)
@@ -342,25 +342,13 @@ int ldpc_engine_gen_bsc_codes(ldpc_engine* e, int8_t* d_out, int64_t b0, int64_t
 int ldpc_engine_profile(ldpc_engine* e, int32_t stride)
 {
     if (!e) { set_error("null engine"); return LDPC_ERR_ARG; }
-    int rc = e->e->collect_stats();
-    if (rc) return rc;
-    for (int c = 0; c < ldpc::K_NCLASS; c++) { e->e->launches[c] = 0; e->e->ms[c] = 0; e->e->sampled[c] = 0; }
-    e->e->profile_stride = stride > 0 ? stride : 0;
-    return LDPC_OK;
+    return e->e->profile(stride);
 }
 
 int ldpc_engine_stats(ldpc_engine* e, ldpc_kernel_stats* out)
 {
     if (!e || !out) { set_error("null argument"); return LDPC_ERR_ARG; }
-    int rc = e->e->collect_stats();
-    if (rc) return rc;
-    std::memset(out, 0, sizeof(*out));
-    for (int c = 0; c < ldpc::K_NCLASS; c++) {
-        out->launches[c] = e->e->launches[c];
-        out->sampled[c] = e->e->sampled[c];
-        out->ms[c] = e->e->ms[c];
-    }
-    return LDPC_OK;
+    return e->e->stats(out);
 }
 
 // ---------------------------------------------------------------------------

@@ -199,7 +199,7 @@ Slot::~Slot()
     (void)hipSetDevice(device);
     if (copy) (void)hipStreamSynchronize(copy.get());
     if (copy_out) (void)hipStreamSynchronize(copy_out.get());
-    if (eng->stream) (void)hipStreamSynchronize(eng->stream);
+    if (eng->stream) (void)hipStreamSynchronize(eng->stream.get());
 }
 
 static int make_slot(const HostGraph* g, int device, int algo, int64_t pool, int64_t xfer, const ldpc_schedule& sched,
@@ -358,7 +358,7 @@ int validate(const ldpc_graph* gc, const HostInput& in, int64_t B, int32_t max_i
 //              copy stream: wait st.dec of chunk c - 2 (the device input is free again),
 //              the chunk's H2D copies (codes in pieces, each crossing while the
 //              next is prepared; or fp64 after the exp / copy), record st.h2d
-//   decode(c)  set_params (integer decoders), tie_base = the chunk's offset in the call
+//   decode(c)  set_params (integer decoders), tie hash base = the chunk's offset in the call
 //              engine stream: wait st.h2d, the decode, record st.dec, [pack_bits, record st.dec]
 //              copy_out stream: wait st.dec (after each record), the D2H copies, record st.d2h
 //   finish(c)  host: wait st.d2h, copy the outputs to the caller's arrays
@@ -515,23 +515,23 @@ struct ShardRun {
             int r = E.set_params(c.q_prec, c.q_step, o.msa_offset, o.tie_seed);
             if (r) return r;
         }
-        E.tie_base = c0(ch);  // tie hash keyed by the codeword's index in this call
-        LDPC_HIP(hipStreamWaitEvent(E.stream, st.h2d.get(), 0));
+        hipStream_t es = E.stream.get();
+        LDPC_HIP(hipStreamWaitEvent(es, st.h2d.get(), 0));
         const double td0 = tick();
         double* d_post = c.post_out ? st.d_post.get() : nullptr;
         int r = st.coded ? E.decode_codes(st.d_code.get(), st.table.data(), st.table_kind, Bc, c.max_iter,
                                           st.d_hard.get(), d_post, o.post_kind, st.d_iters.get(), st.d_valid.get(),
-                                          st.d_in.get())
+                                          st.d_in.get(), c0(ch))
                          : E.decode(st.d_in.get(), in_kind, Bc, c.max_iter, st.d_hard.get(), d_post, o.post_kind,
-                                    st.d_iters.get(), st.d_valid.get());
+                                    st.d_iters.get(), st.d_valid.get(), c0(ch));
         if (r) return r;
         note("api chunk %lld: decode enqueue + drain wait %.3f ms\n", (long long)ch, now_ms() - td0);
-        LDPC_HIP(hipEventRecord(st.dec.get(), E.stream));
+        LDPC_HIP(hipEventRecord(st.dec.get(), es));
         LDPC_HIP(hipStreamWaitEvent(out, st.dec.get(), 0));
         if (st.d_hbits) {  // 1/8 of the bytes across PCIe
             r = E.pack_bits(st.d_hard.get(), st.d_hbits.get(), Bc * (int64_t)N / 8);
             if (r) return r;
-            LDPC_HIP(hipEventRecord(st.dec.get(), E.stream));
+            LDPC_HIP(hipEventRecord(st.dec.get(), es));
             LDPC_HIP(hipStreamWaitEvent(out, st.dec.get(), 0));
             LDPC_HIP(hipMemcpyAsync(st.h_hbits.get(), st.d_hbits.get(), (size_t)Bc * N / 8, hipMemcpyDeviceToHost, out));
         } else {
