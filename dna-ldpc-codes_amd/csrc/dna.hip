@@ -31,6 +31,11 @@
 // index (the reference's rs_dec.exe, decoder.py:59-92), k_strands_write lays
 // codewords out as the strands that get synthesised (index prefix + payload,
 // the format of original files/final_DNA.txt).
+//
+// The step after it, the trial loop of decoder.py:541-664 with the decoder
+// input kept on the device (dna_trial.hpp): the kernels,
+// the handle and the ldpc_trial_* entry points are dna_trial_kernels.hpp,
+// included last.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,6 +47,8 @@
 #include "../../include/ldpc_amd.h"
 #include "engine.hpp"
 #include "dna_plan.hpp"
+#include "dna_trial.hpp"
+#include "host_decode.hpp"  // ldpc_graph
 #include "rs_index.hpp"
 #include "star_align.hpp"
 
@@ -59,6 +66,49 @@ __device__ __forceinline__ bool bit_is_zero(uint8_t c, bool hi)
     return c == 'A' || c == 'G';
 }
 
+// The count rule of one bit b = 2 * k + h of a strand of kind kd whose rows are
+// r0 .. r1 - 1 (decoder.py:266-320, :442-497): *n = the count difference, the
+// entry is *n * L; *is_int: the reference leaves an int 0.  Shared by
+// k_dna_llr and k_dna_codes (dna_trial_kernels.hpp).
+__device__ __forceinline__ void dna_bit_rule(int kd, int64_t r0, int64_t r1, const uint8_t* __restrict__ rows,
+                                             const int32_t* __restrict__ row_q, int32_t nt, int32_t k, int h, int* n,
+                                             bool* is_int)
+{
+    const int b = 2 * k + h, last_bit = 2 * nt - 1;
+    *n = 0;
+    *is_int = true;
+    if (kd == 1) {
+        int c0 = 0, c1 = 0, q0 = 0, q1 = 0;
+        for (int64_t r = r0; r < r1; r++) {
+            const int q = row_q[r];
+            if (b == last_bit && q < kQSkip) continue;
+            if (bit_is_zero(rows[r * nt + k], h == 0)) { c0++; q0 += q; }
+            else { c1++; q1 += q; }
+        }
+        if (b == last_bit && c0 == 1 && c1 == 1) {
+            if (q0 < kQSkip && q1 >= kQHigh) { *n = -2; *is_int = false; }
+            else if (q0 >= kQHigh && q1 < kQSkip) { *n = 2; *is_int = false; }
+        } else {
+            *n = c0 - c1;
+            *is_int = false;
+        }
+    } else if (kd == 2 && b == last_bit && r1 > r0) {
+        if (row_q[r0] > kQHigh) {
+            *n = bit_is_zero(rows[r0 * nt], false) ? 1 : -1;
+            *is_int = false;
+        }
+    } else if (kd == 3 && b == last_bit) {
+        int c0 = 0, c1 = 0;
+        for (int64_t r = r0; r < r1; r++) {
+            if (row_q[r] <= kQHigh) continue;
+            if (bit_is_zero(rows[r * nt], false)) c0++;
+            else c1++;
+        }
+        *n = c0 - c1;
+        *is_int = false;
+    }
+}
+
 // Every entry is k * L for an integer count difference k (decoder.py:297-314;
 // the +-2L / +-L special cases included), so the kernel can hand the decoder
 // its int8 codes directly (codes != nullptr): k saturated to [-127, 127], and
@@ -74,41 +124,11 @@ __global__ void __launch_bounds__(256) k_dna_llr(const int32_t* __restrict__ kin
     if (s >= S) return;
     const int kd = kind[s];
     const int64_t r0 = row_ptr[s], r1 = row_ptr[s + 1];
-    const int last_bit = 2 * nt - 1;
     for (int h = 0; h < 2; h++) {
         const int b = 2 * k + h;
-        int n = 0;  // the count difference: the entry is n * L (0 for an int-0 entry)
-        bool is_int = true;
-        if (kd == 1) {
-            int c0 = 0, c1 = 0, q0 = 0, q1 = 0;
-            for (int64_t r = r0; r < r1; r++) {
-                const int q = row_q[r];
-                if (b == last_bit && q < kQSkip) continue;
-                if (bit_is_zero(rows[r * nt + k], h == 0)) { c0++; q0 += q; }
-                else { c1++; q1 += q; }
-            }
-            if (b == last_bit && c0 == 1 && c1 == 1) {
-                if (q0 < kQSkip && q1 >= kQHigh) { n = -2; is_int = false; }
-                else if (q0 >= kQHigh && q1 < kQSkip) { n = 2; is_int = false; }
-            } else {
-                n = c0 - c1;
-                is_int = false;
-            }
-        } else if (kd == 2 && b == last_bit && r1 > r0) {
-            if (row_q[r0] > kQHigh) {
-                n = bit_is_zero(rows[r0 * nt], false) ? 1 : -1;
-                is_int = false;
-            }
-        } else if (kd == 3 && b == last_bit) {
-            int c0 = 0, c1 = 0;
-            for (int64_t r = r0; r < r1; r++) {
-                if (row_q[r] <= kQHigh) continue;
-                if (bit_is_zero(rows[r * nt], false)) c0++;
-                else c1++;
-            }
-            n = c0 - c1;
-            is_int = false;
-        }
+        int n;  // the count difference: the entry is n * L (0 for an int-0 entry)
+        bool is_int;
+        dna_bit_rule(kd, r0, r1, rows, row_q, nt, k, h, &n, &is_int);
         // (double)n * L: the reference's (count_0 - count_1) * math.log(...),
         // and 2.0 * L, L, -L for the special cases -- the same doubles
         llr[(size_t)b * S + s] = is_int ? 0.0 : (double)n * L;
@@ -1116,3 +1136,6 @@ int ldpc_dna_reads_llr(const uint8_t* seqs, const int64_t* offsets, const int32_
 }
 
 }  // extern "C"
+
+// --- the trial handle (dna_trial.hpp) -------------------
+#include "dna_trial_kernels.hpp"

@@ -1,0 +1,441 @@
+// dna_trial_kernels.hpp -- the trial handle: the kernels
+// and the device backend of dna_trial.hpp's control flow, and the ldpc_trial_*
+// entry points.  Included at the end of dna.hip, which has the planner
+// (plan_device) and the count rule (dna_bit_rule) it reuses.
+//
+// Everything of a run is enqueued on the engine's stream, the planner excepted:
+// its kernels run on the null stream, and the engine's stream waits for an
+// event recorded there before the code kernel starts.  Every index loaded from
+// device memory is range-checked before use; a failed check sets the handle's
+// flag word and the call fails with LDPC_ERR_DEVICE.
+//
+//   k_dna_codes      k_dna_llr's count rule, int8 codes and the overflow word only
+//   k_trial_stats    one pass over hard, codes and truth: errors per row,
+//                    re_decode per column, integer atomics only
+//   k_trial_gather   rows of the code matrix -> the contiguous batch of a second decode
+//   k_trial_scatter  rows of a second decode's hard bits -> their rows of hard
+#pragma once
+
+namespace ldpc {
+namespace {
+
+// k_dna_llr without the fp64 matrix and the mask: thread (strand s, nucleotide
+// k) writes the codes of bits 2k and 2k + 1 with the same rule and the same
+// saturation, so the bytes are k_dna_llr's codes.
+__global__ void __launch_bounds__(256) k_dna_codes(const int32_t* __restrict__ kind,
+                                                   const int64_t* __restrict__ row_ptr,
+                                                   const uint8_t* __restrict__ rows,
+                                                   const int32_t* __restrict__ row_q, int32_t S, int32_t nt,
+                                                   int8_t* __restrict__ codes, int32_t* __restrict__ overflow)
+{
+    const int32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t k = blockIdx.y;
+    if (s >= S) return;
+    const int kd = kind[s];
+    const int64_t r0 = row_ptr[s], r1 = row_ptr[s + 1];
+    for (int h = 0; h < 2; h++) {
+        int n;
+        bool is_int;
+        dna_bit_rule(kd, r0, r1, rows, row_q, nt, k, h, &n, &is_int);
+        codes[(size_t)(2 * k + h) * S + s] = (int8_t)max(-127, min(127, n));
+        if (n > 127 || n < -127) *overflow = 1;
+    }
+}
+
+constexpr int kStatCols = 4;     // columns per thread (one 4-byte load of each matrix when N % 4 == 0)
+constexpr int kStatRows = 16;    // rows per block
+constexpr int kStatThreads = 256;
+
+// 4 bytes of row `p` from column c0: one dword when `vec` (N % 4 == 0, so every
+// row starts 4-byte aligned), else the bytes below N one by one (others 0).
+__device__ __forceinline__ uint32_t load4(const uint8_t* __restrict__ p, int64_t c0, int32_t N, bool vec)
+{
+    if (vec) return *reinterpret_cast<const uint32_t*>(p + c0);
+    uint32_t v = 0;
+    for (int c = 0; c < kStatCols; c++)
+        if (c0 + c < N) v |= (uint32_t)p[c0 + c] << (8 * c);
+    return v;
+}
+
+// Block (x, y): columns [x * 1024, x * 1024 + 1024), batch rows [y * 16, y * 16
+// + 16).  Batch row k is row k of hard [B][N]; its codes and truth are row
+// rows[k] (rows null: k) of codes / truth [n_rows][N].  errors[k] += number of
+// hard != truth (truth null: left alone), re_decode[j] += hard != (code < 0)
+// (re_decode null: left alone).  Column sums stay in registers over the row
+// loop; a row's count is reduced over the wave, one atomic per wave.
+__global__ void __launch_bounds__(kStatThreads) k_trial_stats(const uint8_t* __restrict__ hard,
+                                                              const int8_t* __restrict__ codes,
+                                                              const uint8_t* __restrict__ truth,
+                                                              const int32_t* __restrict__ rows, int32_t B,
+                                                              int32_t n_rows, int32_t N, int32_t* __restrict__ errors,
+                                                              int32_t* __restrict__ re_decode,
+                                                              int32_t* __restrict__ bad)
+{
+    const bool vec = (N & 3) == 0;
+    const int64_t c0 = ((int64_t)blockIdx.x * kStatThreads + threadIdx.x) * kStatCols;
+    const bool live = c0 < N;  // with vec, c0 + 4 <= N as well
+    const int32_t k0 = (int32_t)blockIdx.y * kStatRows;
+    const int32_t k1 = k0 + kStatRows < B ? k0 + kStatRows : B;
+    int32_t col[kStatCols] = {0, 0, 0, 0};
+    for (int32_t k = k0; k < k1; k++) {  // (k and i are the same for the whole block)
+        const int32_t i = rows ? rows[k] : k;
+        if (i < 0 || i >= n_rows) {
+            if (threadIdx.x == 0) *bad = 1;
+            continue;
+        }
+        int32_t e = 0;
+        if (live) {
+            const uint32_t h = load4(hard + (size_t)k * N, c0, N, vec);
+            if (re_decode) {
+                const uint32_t cd = load4(reinterpret_cast<const uint8_t*>(codes) + (size_t)i * N, c0, N, vec);
+#pragma unroll
+                for (int c = 0; c < kStatCols; c++)
+                    col[c] += ((h >> (8 * c)) & 0xffu) != ((cd >> (8 * c + 7)) & 1u);  // the code's sign bit
+            }
+            if (truth) {
+                const uint32_t d = h ^ load4(truth + (size_t)i * N, c0, N, vec);
+#pragma unroll
+                for (int c = 0; c < kStatCols; c++) e += ((d >> (8 * c)) & 0xffu) != 0;
+            }
+        }
+        if (truth) {
+            for (int o = 32; o > 0; o >>= 1) e += __shfl_down(e, o, 64);
+            if ((threadIdx.x & 63) == 0 && e) atomicAdd(&errors[k], e);
+        }
+    }
+    if (live && re_decode)
+        for (int c = 0; c < kStatCols; c++)
+            if (c0 + c < N && col[c]) atomicAdd(&re_decode[c0 + c], col[c]);
+}
+
+constexpr int kCopyThreads = 256;
+constexpr int kCopyBytes = 16;  // per thread
+
+// Bytes [x * 4096, x * 4096 + 4096) of one row: 16 per thread, as one uint4
+// when `vec` (N % 16 == 0 and both matrices 16-byte aligned, so every row is),
+// else byte by byte.
+__device__ __forceinline__ void copy_row_piece(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int32_t N,
+                                               bool vec)
+{
+    const int64_t o = ((int64_t)blockIdx.x * kCopyThreads + threadIdx.x) * kCopyBytes;
+    if (o >= N) return;
+    if (vec) {
+        *reinterpret_cast<uint4*>(dst + o) = *reinterpret_cast<const uint4*>(src + o);
+        return;
+    }
+    for (int c = 0; c < kCopyBytes && o + c < N; c++) dst[o + c] = src[o + c];
+}
+
+// out[k] = src[rows[k]] for k = blockIdx.y < F; src has n_rows rows.
+__global__ void __launch_bounds__(kCopyThreads) k_trial_gather(const uint8_t* __restrict__ src,
+                                                               const int32_t* __restrict__ rows, int32_t n_rows,
+                                                               int32_t N, int32_t vec, uint8_t* __restrict__ out,
+                                                               int32_t* __restrict__ bad)
+{
+    const int32_t k = (int32_t)blockIdx.y, i = rows[k];
+    if (i < 0 || i >= n_rows) {
+        if (threadIdx.x == 0) *bad = 1;
+        return;
+    }
+    copy_row_piece(src + (size_t)i * N, out + (size_t)k * N, N, vec != 0);
+}
+
+// dst[rows[pos[q]]] = batch[pos[q]] for q = blockIdx.y; batch has F rows, dst n_rows.
+__global__ void __launch_bounds__(kCopyThreads) k_trial_scatter(const uint8_t* __restrict__ batch,
+                                                                const int32_t* __restrict__ rows,
+                                                                const int32_t* __restrict__ pos, int32_t F,
+                                                                int32_t n_rows, int32_t N, int32_t vec,
+                                                                uint8_t* __restrict__ dst, int32_t* __restrict__ bad)
+{
+    const int32_t k = pos[blockIdx.y];
+    if (k < 0 || k >= F) {
+        if (threadIdx.x == 0) *bad = 1;
+        return;
+    }
+    const int32_t i = rows[k];
+    if (i < 0 || i >= n_rows) {
+        if (threadIdx.x == 0) *bad = 1;
+        return;
+    }
+    copy_row_piece(batch + (size_t)k * N, dst + (size_t)i * N, N, vec != 0);
+}
+
+}  // namespace
+}  // namespace ldpc
+
+// The handle: everything a run needs on the device, allocated once.
+struct ldpc_trial {
+    const ldpc::HostGraph* g = nullptr;
+    int32_t device = 0, algo = 0, n_cw = 0, N = 0;
+    bool genie = false;
+    int32_t B = 0, F = 0;      // rows of the current run; rows of its last second-decode batch
+    ldpc::Engine eng;
+    ldpc::Event planned;       // null stream -> engine stream
+    ldpc::dev_ptr<uint8_t> truth, hard, valid, bhard, bvalid;
+    ldpc::dev_ptr<int8_t> codes, bcodes;
+    ldpc::dev_ptr<int32_t> iters, biters, errors, re_decode, rows, pos;
+    ldpc::dev_ptr<int32_t> ctl;  // [0] a failed range check, [1] the code kernel's overflow word
+    bool batch = false;          // the last decode went to bhard / bvalid
+
+    ~ldpc_trial()
+    {
+        (void)hipSetDevice(device);
+        if (eng.stream) (void)hipStreamSynchronize(eng.stream.get());
+    }
+};
+
+namespace ldpc {
+namespace {
+
+constexpr int64_t kTrialPoolMax = 1024;  // host_decode.cpp's kExplicitPoolMax: shards up to here get a pool of their size
+
+// The device backend of trial::run.
+struct TrialDev {
+    ldpc_trial& t;
+    hipStream_t s;
+    explicit TrialDev(ldpc_trial& tr) : t(tr), s(tr.eng.stream.get()) {}
+    bool has_truth() const { return t.genie; }
+    bool vec16() const { return t.N % 16 == 0; }  // (hipMalloc's bases are 256-byte aligned)
+    // the flag word, after the stream has been waited for
+    int check_flag(const char* what)
+    {
+        int32_t bad = 0;
+        LDPC_HIP(hipMemcpyAsync(&bad, t.ctl.get(), sizeof bad, hipMemcpyDeviceToHost, s));
+        if (int rc = t.eng.sync()) return rc;
+        if (bad) {
+            set_error(std::string("ldpc_trial: a row index failed its range check in ") + what);
+            return LDPC_ERR_DEVICE;
+        }
+        return LDPC_OK;
+    }
+    int decode(const int32_t* rows, int64_t B, const double* table, int32_t max_iter)
+    {
+        t.batch = rows != nullptr;
+        if (!rows)
+            return t.eng.decode_codes(t.codes.get(), table, LDPC_IN_LLR, B, max_iter, t.hard.get(), nullptr,
+                                      LDPC_POST_LLR, t.iters.get(), t.valid.get());
+        t.F = (int32_t)B;
+        // (rows stays as it is until the stats call that follows has waited for the stream)
+        LDPC_HIP(hipMemcpyAsync(t.rows.get(), rows, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, s));
+        const dim3 grid((unsigned)(((int64_t)t.N + kCopyThreads * kCopyBytes - 1) / (kCopyThreads * kCopyBytes)),
+                        (unsigned)B);
+        hipLaunchKernelGGL(k_trial_gather, grid, dim3(kCopyThreads), 0, s,
+                           reinterpret_cast<const uint8_t*>(t.codes.get()), t.rows.get(), t.B, t.N, (int32_t)vec16(),
+                           reinterpret_cast<uint8_t*>(t.bcodes.get()), t.ctl.get());
+        LDPC_HIP(hipGetLastError());
+        return t.eng.decode_codes(t.bcodes.get(), table, LDPC_IN_LLR, B, max_iter, t.bhard.get(), nullptr,
+                                  LDPC_POST_LLR, t.biters.get(), t.bvalid.get());
+    }
+    int stats(const int32_t* rows, int64_t B, int32_t* errors, uint8_t* valid, int32_t* re_decode)
+    {
+        LDPC_HIP(hipMemsetAsync(t.errors.get(), 0, sizeof(int32_t) * (size_t)B, s));
+        if (re_decode) LDPC_HIP(hipMemsetAsync(t.re_decode.get(), 0, sizeof(int32_t) * (size_t)t.N, s));
+        const dim3 grid((unsigned)(((int64_t)t.N + kStatThreads * kStatCols - 1) / (kStatThreads * kStatCols)),
+                        (unsigned)((B + kStatRows - 1) / kStatRows));
+        hipLaunchKernelGGL(k_trial_stats, grid, dim3(kStatThreads), 0, s, t.batch ? t.bhard.get() : t.hard.get(),
+                           t.codes.get(), t.genie ? t.truth.get() : nullptr, rows ? t.rows.get() : nullptr,
+                           (int32_t)B, t.B, t.N, t.errors.get(), re_decode ? t.re_decode.get() : nullptr,
+                           t.ctl.get());
+        LDPC_HIP(hipGetLastError());
+        LDPC_HIP(hipMemcpyAsync(errors, t.errors.get(), sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, s));
+        LDPC_HIP(hipMemcpyAsync(valid, (t.batch ? t.bvalid : t.valid).get(), (size_t)B, hipMemcpyDeviceToHost, s));
+        if (re_decode)
+            LDPC_HIP(hipMemcpyAsync(re_decode, t.re_decode.get(), sizeof(int32_t) * (size_t)t.N,
+                                    hipMemcpyDeviceToHost, s));
+        return check_flag("k_trial_stats / k_trial_gather");
+    }
+    int keep(const int32_t* rows, const int32_t* pos, int64_t n)
+    {
+        (void)rows;  // on the device since this decode's gather
+        LDPC_HIP(hipMemcpyAsync(t.pos.get(), pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+        const dim3 grid((unsigned)(((int64_t)t.N + kCopyThreads * kCopyBytes - 1) / (kCopyThreads * kCopyBytes)),
+                        (unsigned)n);
+        hipLaunchKernelGGL(k_trial_scatter, grid, dim3(kCopyThreads), 0, s, t.bhard.get(), t.rows.get(), t.pos.get(),
+                           t.F, t.B, t.N, (int32_t)vec16(), t.hard.get(), t.ctl.get());
+        LDPC_HIP(hipGetLastError());
+        return check_flag("k_trial_scatter");
+    }
+};
+
+int trial_create(const ldpc_graph* g, int32_t device, int32_t algo, int32_t n_cw, const uint8_t* codewords,
+                 const ldpc_schedule* schedule, std::unique_ptr<ldpc_trial>& out)
+{
+    if (!g) { set_error("ldpc_trial_create: null graph"); return LDPC_ERR_ARG; }
+    if (algo != LDPC_ALGO_BP && algo != LDPC_ALGO_MSA) {
+        set_error("ldpc_trial_create: algo must be LDPC_ALGO_BP or LDPC_ALGO_MSA");
+        return LDPC_ERR_ARG;
+    }
+    const int64_t N = g->h.N;
+    if (n_cw < 1 || N < 1 || (int64_t)n_cw > INT64_MAX / 8 / N) {
+        set_error("ldpc_trial_create: n_cw must be >= 1 (and n_cw * N addressable)");
+        return LDPC_ERR_ARG;
+    }
+    if (n_cw > 65535) {  // one grid row per codeword of a second decode
+        set_error("ldpc_trial_create: more than 65535 codewords per trial are not supported");
+        return LDPC_ERR_UNSUPPORTED;
+    }
+    auto t = std::make_unique<ldpc_trial>();
+    t->g = &g->h;
+    t->device = device;
+    t->algo = algo;
+    t->n_cw = n_cw;
+    t->N = (int32_t)N;
+    t->genie = codewords != nullptr;
+    int rc;
+    if ((rc = select_device("ldpc_trial_create", device))) return rc;
+    const int64_t pool = n_cw <= kTrialPoolMax ? ((int64_t)n_cw + 63) / 64 * 64 : 0;
+    if ((rc = t->eng.init(t->g, device, algo, pool, schedule))) return rc;
+    const size_t n = (size_t)n_cw, mat = n * (size_t)N;
+    if ((t->genie && (rc = upload(t->truth, codewords, mat))) || (rc = dev_alloc(t->codes, mat)) ||
+        (rc = dev_alloc(t->bcodes, mat)) || (rc = dev_alloc(t->hard, mat)) || (rc = dev_alloc(t->bhard, mat)) ||
+        (rc = dev_alloc(t->valid, n)) || (rc = dev_alloc(t->bvalid, n)) || (rc = dev_alloc(t->iters, n)) ||
+        (rc = dev_alloc(t->biters, n)) || (rc = dev_alloc(t->errors, n)) || (rc = dev_alloc(t->re_decode, (size_t)N)) ||
+        (rc = dev_alloc(t->rows, n)) || (rc = dev_alloc(t->pos, n)) || (rc = dev_alloc(t->ctl, 2)) ||
+        (rc = make_event(t->planned)))
+        return rc;
+    out = std::move(t);
+    return LDPC_OK;
+}
+
+// The control flow over the handle's code matrix (rows [0, B) are in place,
+// enqueued on the engine's stream), and the outputs that stay on the device.
+int trial_run(ldpc_trial& t, int32_t B, double eps, int32_t max_iter, int32_t faithful, ldpc_trial_result* out)
+{
+    t.B = B;
+    TrialDev be(t);
+    if (int rc = trial::run(be, B, t.N, eps, max_iter, faithful != 0, out)) return rc;
+    hipStream_t s = be.s;
+    if (out->hard) LDPC_HIP(hipMemcpyAsync(out->hard, t.hard.get(), (size_t)B * (size_t)t.N, hipMemcpyDeviceToHost, s));
+    if (out->iters) LDPC_HIP(hipMemcpyAsync(out->iters, t.iters.get(), sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, s));
+    if (out->valid) LDPC_HIP(hipMemcpyAsync(out->valid, t.valid.get(), (size_t)B, hipMemcpyDeviceToHost, s));
+    return t.eng.sync();
+}
+
+int trial_run_codes(ldpc_trial* t, const int8_t* codes, int64_t B, double eps, int32_t max_iter, int32_t faithful,
+                    ldpc_trial_result* out)
+{
+    const std::string who = "ldpc_trial_run_codes: ";
+    if (!t || !codes) { set_error(who + "null handle or codes"); return LDPC_ERR_ARG; }
+    if (B < 1 || B > t->n_cw) { set_error(who + "B must be in 1 .. n_cw"); return LDPC_ERR_ARG; }
+    const std::string err = trial::check_args(B, t->N, eps, max_iter, out);
+    if (!err.empty()) { set_error(who + err); return LDPC_ERR_ARG; }
+    LDPC_HIP(hipSetDevice(t->device));
+    hipStream_t s = t->eng.stream.get();
+    LDPC_HIP(hipMemsetAsync(t->ctl.get(), 0, 2 * sizeof(int32_t), s));
+    LDPC_HIP(hipMemcpyAsync(t->codes.get(), codes, (size_t)B * (size_t)t->N, hipMemcpyHostToDevice, s));
+    LDPC_HIP(hipStreamSynchronize(s));  // the caller's buffer is free whichever way the call ends
+    out->codes_exact = 1;
+    out->t_llr_s = 0.0;
+    return trial_run(*t, (int32_t)B, eps, max_iter, faithful, out);
+}
+
+int trial_run_reads(ldpc_trial* t, const plan::Args& a, int64_t workspace_bytes, double eps, int32_t max_iter,
+                    int32_t faithful, ldpc_trial_result* out)
+{
+    const std::string who = "ldpc_trial_run_reads";
+    if (!t) { set_error(who + ": null handle"); return LDPC_ERR_ARG; }
+    const std::string err = trial::check_args(t->n_cw, t->N, eps, max_iter, out);
+    if (!err.empty()) { set_error(who + ": " + err); return LDPC_ERR_ARG; }
+    if (a.payload_nt < 1 || 2 * (int64_t)a.payload_nt != t->n_cw || a.n_strands != t->N) {
+        set_error(who + ": needs 2 * payload_nt == n_cw and n_strands == N");
+        return LDPC_ERR_ARG;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    PlanDev pd;
+    if (int rc = plan_device(who, a, false, t->device, workspace_bytes, &pd)) return rc;
+    // the planner's kernels ran on the null stream: the engine's stream waits for them
+    hipStream_t s = t->eng.stream.get();
+    LDPC_HIP(hipEventRecord(t->planned.get(), nullptr));
+    LDPC_HIP(hipStreamWaitEvent(s, t->planned.get(), 0));
+    LDPC_HIP(hipMemsetAsync(t->ctl.get(), 0, 2 * sizeof(int32_t), s));
+    const dim3 grid((unsigned)((a.n_strands + 255) / 256), (unsigned)a.payload_nt);
+    hipLaunchKernelGGL(k_dna_codes, grid, dim3(256), 0, s, pd.kind.get(), pd.row_ptr.get(), pd.rows.get(),
+                       pd.row_q.get(), a.n_strands, a.payload_nt, t->codes.get(), t->ctl.get() + 1);
+    LDPC_HIP(hipGetLastError());
+    int32_t ov = 0;
+    LDPC_HIP(hipMemcpyAsync(&ov, t->ctl.get() + 1, sizeof ov, hipMemcpyDeviceToHost, s));
+    LDPC_HIP(hipStreamSynchronize(s));  // the plan is released below; ov is read
+    out->codes_exact = ov ? 0 : 1;
+    out->t_llr_s = trial::seconds_since(t0);
+    if (ov) {
+        set_error(who + ": a count difference is outside int8 (codes_exact = 0): the resident trial cannot "
+                        "represent this input; use ldpc_dna_reads_llr and the fp64 decode");
+        return LDPC_ERR_UNSUPPORTED;
+    }
+    return trial_run(*t, t->n_cw, eps, max_iter, faithful, out);
+}
+
+template <class F>
+int trial_guard(const char* who, F&& f)
+{
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        set_error(std::string(who) + ": out of host memory");
+        return LDPC_ERR_DEVICE;
+    }
+}
+
+}  // namespace
+}  // namespace ldpc
+
+extern "C" {
+
+int ldpc_dna_trial_host(const int8_t* codes, int32_t n_cw, int32_t N, const uint8_t* codewords,
+                        ldpc_trial_decode_fn decode, void* user, double eps, int32_t max_iter, int32_t faithful,
+                        ldpc_trial_result* out)
+{
+    return ldpc::trial_guard("ldpc_dna_trial_host", [&] {
+        std::string err;
+        const int rc = ldpc::trial::run_host(codes, n_cw, N, codewords, decode, user, eps, max_iter, faithful, out, &err);
+        if (rc) set_error("ldpc_dna_trial_host: " + err);
+        return rc;
+    });
+}
+
+ldpc_trial* ldpc_trial_create(const ldpc_graph* g, int32_t device, int32_t algo, int32_t n_cw,
+                              const uint8_t* codewords, const ldpc_schedule* schedule, int* err)
+{
+    std::unique_ptr<ldpc_trial> t;
+    const int rc = ldpc::trial_guard("ldpc_trial_create",
+                                     [&] { return ldpc::trial_create(g, device, algo, n_cw, codewords, schedule, t); });
+    if (err) *err = rc;
+    return rc ? nullptr : t.release();
+}
+
+void ldpc_trial_free(ldpc_trial* t) { delete t; }
+
+int ldpc_trial_run_reads(ldpc_trial* t, const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths,
+                         const int32_t* quals, int64_t n_reads, const int32_t* index_vals, const int32_t* strands,
+                         int32_t n_strands, int32_t payload_nt, int32_t align, int64_t workspace_bytes, double eps,
+                         int32_t max_iter, int32_t faithful, ldpc_trial_result* out)
+{
+    return ldpc::trial_guard("ldpc_trial_run_reads", [&] {
+        return ldpc::trial_run_reads(t, plan_args(seqs, offsets, lengths, quals, n_reads, index_vals, strands, n_strands,
+                                                  payload_nt, align, out ? out->kind : nullptr, nullptr, nullptr,
+                                                  nullptr, out ? out->stats : nullptr),
+                                     workspace_bytes, eps, max_iter, faithful, out);
+    });
+}
+
+int ldpc_trial_run_codes(ldpc_trial* t, const int8_t* codes, int64_t B, double eps, int32_t max_iter,
+                         int32_t faithful, ldpc_trial_result* out)
+{
+    return ldpc::trial_guard("ldpc_trial_run_codes",
+                             [&] { return ldpc::trial_run_codes(t, codes, B, eps, max_iter, faithful, out); });
+}
+
+int ldpc_trial_read_codes(ldpc_trial* t, int8_t* codes, int64_t B)
+{
+    if (!t || !codes || B < 0 || B > t->n_cw) {
+        set_error("ldpc_trial_read_codes: bad arguments");
+        return LDPC_ERR_ARG;
+    }
+    LDPC_HIP(hipSetDevice(t->device));
+    hipStream_t s = t->eng.stream.get();
+    LDPC_HIP(hipMemcpyAsync(codes, t->codes.get(), (size_t)B * (size_t)t->N, hipMemcpyDeviceToHost, s));
+    LDPC_HIP(hipStreamSynchronize(s));
+    return LDPC_OK;
+}
+
+}  // extern "C"

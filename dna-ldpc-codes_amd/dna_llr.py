@@ -122,6 +122,21 @@ class LlrResult:
                                                 mask.ctypes.data_as(C.c_void_p), llr.shape[0], llr.shape[1]))
 
 
+class TrialResult(C.Structure):
+    """ldpc_trial_result (include/ldpc_amd.h): counts, caller-owned arrays
+    (any may be null) and the stage times of one trial."""
+    _fields_ = [(k, C.c_int32) for k in ("n", "first_success", "second_success", "second_iterations", "n_fail_first",
+                                         "n_fail_second", "n_erasure", "codes_exact")] + \
+               [(k, C.c_void_p) for k in ("fail_first", "fail_second", "first_errors", "second_errors",
+                                          "erasure_index", "hard", "iters", "valid", "kind", "stats")] + \
+               [(k, C.c_double) for k in ("t_llr_s", "t_first_s", "t_second_s")]
+
+
+# ldpc_trial_decode_fn: (user, codes, table, B, max_iter, hard, valid) -> int
+TRIAL_DECODE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int8), C.POINTER(C.c_double), C.c_int64, C.c_int32,
+                              C.POINTER(C.c_uint8), C.POINTER(C.c_uint8))
+
+
 def _lib():
     import ldpc_amd
     L = ldpc_amd.lib()
@@ -143,6 +158,16 @@ def _lib():
         L.ldpc_dna_plan.argtypes = [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp]
         L.ldpc_dna_reads_llr.argtypes = [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i64, C.c_double, vp, vp,
                                          vp, vp, vp, vp]
+        pres = C.POINTER(TrialResult)
+        L.ldpc_dna_trial_host.argtypes = [vp, i32, i32, vp, TRIAL_DECODE_FN, vp, C.c_double, i32, i32, pres]
+        L.ldpc_trial_create.argtypes = [vp, i32, i32, i32, vp, C.POINTER(ldpc_amd.Schedule), C.POINTER(C.c_int)]
+        L.ldpc_trial_create.restype = vp
+        L.ldpc_trial_free.argtypes = [vp]
+        L.ldpc_trial_free.restype = None
+        L.ldpc_trial_run_reads.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i64, C.c_double, i32, i32,
+                                           pres]
+        L.ldpc_trial_run_codes.argtypes = [vp, vp, i64, C.c_double, i32, i32, pres]
+        L.ldpc_trial_read_codes.argtypes = [vp, vp, i64]
         L._dna_bound = True
     return ldpc_amd, L
 

@@ -24,8 +24,13 @@ The first decode's LLRs are count differences times ln((1-eps)/eps)
 LlrResult.codes, made by the LLR kernel itself), the GPU decode_fn takes the
 codes and the 256-entry table k * unit (Graph.decode_codes) -- the same
 doubles, without the host lattice pass over the fp64 matrix that the fp64
-entry needs.  The second decode's rescaled LLRs are off that lattice and keep
-the fp64 entry.
+entry needs.  The second decode's rescaled LLRs are off that lattice, but each
+is still a function of its code alone: the rescaled input of a failed codeword
+is its same codes with the 256-entry table rescale(code_table(unit), eps,
+eps2).  decode_trial keeps sending them through the fp64 entry; the library's
+trial (ResidentTrial, decode_trial_host; csrc/dna_trial.hpp, DESIGN.md sec.
+8.8) decodes every stage from the one int8 matrix, which then never leaves the
+device.
 """
 from __future__ import annotations
 
@@ -191,6 +196,216 @@ def trial_from_raw_reads(raw_reads, codewords: np.ndarray, eps: float = 0.02, ma
                            faithful=faithful, device=device)
     res.update(t_index_s=t_index, n_reads_dropped=hist[-1], cnumerr_hist=hist)
     return res
+
+
+class _TrialOut:
+    """The caller-owned arrays of one ldpc_trial_result and the dict made of them."""
+
+    def __init__(self, n_cw: int, N: int, n_strands: int = 0):
+        import ctypes as C
+
+        import dna_llr
+        self.n_cw, self.N = n_cw, N
+        self.a = {k: np.zeros(n_cw, np.int32) for k in ("fail_first", "fail_second", "first_errors", "second_errors",
+                                                        "iters")}
+        self.a.update(erasure_index=np.zeros(N, np.int32), hard=np.zeros((n_cw, N), np.uint8),
+                      valid=np.zeros(n_cw, np.uint8))
+        if n_strands:
+            self.a.update(kind=np.zeros(n_strands, np.int32), stats=np.zeros(dna_llr.N_PLAN_STATS, np.int64))
+        self.r = dna_llr.TrialResult()
+        for k, v in self.a.items():
+            setattr(self.r, k, v.ctypes.data_as(C.c_void_p))
+
+    def ref(self):
+        import ctypes as C
+        return C.byref(self.r)
+
+    def result(self) -> Dict:
+        r, a, n = self.r, self.a, self.r.n
+        fail = a["fail_first"][:r.n_fail_first].tolist()
+        return {
+            "first_success": r.first_success, "second_success": r.second_success, "n": n,
+            "fail_first": fail, "fail_second": a["fail_second"][:r.n_fail_second].tolist(),
+            "second_iterations": r.second_iterations,
+            "first_errors": {i: int(a["first_errors"][i - 1]) for i in fail},
+            "second_errors": {i + 1: int(v) for i, v in enumerate(a["second_errors"][:n]) if v != -2},
+            "erasure_index": a["erasure_index"][:r.n_erasure].tolist(), "hard": a["hard"][:n],
+            "t_first_s": r.t_first_s, "t_second_s": r.t_second_s,
+            "iters": a["iters"][:n], "valid": a["valid"][:n].astype(bool),
+        }
+
+
+def decode_trial_host(codes: np.ndarray, codewords: Optional[np.ndarray], decode_cb, eps: float = 0.02,
+                      max_iter: int = 200, faithful: bool = True) -> Dict:
+    """decode_trial in the library on host buffers (ldpc_dna_trial_host,
+    csrc/dna_trial.hpp): codes int8 [n_cw][N] are the whole input, every decode
+    goes to decode_cb(codes [B][N], table [256], max_iter) -> (hard [B][N],
+    valid [B]), the decode of table[codes + 128].  codewords None: genie-less
+    (a row fails iff its valid flag is 0; its error count reads -1).  The
+    result has decode_trial's keys (plus valid; iters is not reported by a
+    callback and reads 0)."""
+    import dna_llr
+    mod, L = dna_llr._lib()
+    k = np.ascontiguousarray(codes)
+    if k.dtype != np.int8 or k.ndim != 2:
+        raise ValueError("codes must be int8 [n_cw][N]")
+    n_cw, N = k.shape
+    cw = None
+    if codewords is not None:
+        cw = np.ascontiguousarray(codewords, np.uint8)
+        if cw.shape != k.shape:
+            raise ValueError("codewords must have the shape of codes")
+    raised = []
+
+    def cb(_user, p_codes, p_table, B, it, p_hard, p_valid):
+        try:
+            c = np.ctypeslib.as_array(p_codes, shape=(B, N))
+            t = np.ctypeslib.as_array(p_table, shape=(256,))
+            hard, valid = decode_cb(c.copy(), t.copy(), int(it))
+            np.ctypeslib.as_array(p_hard, shape=(B, N))[:] = hard
+            np.ctypeslib.as_array(p_valid, shape=(B,))[:] = valid
+            return 0
+        except BaseException as e:  # noqa: BLE001 -- no exception may cross the C frames
+            raised.append(e)
+            return mod.LDPC_ERR_ARG
+
+    out = _TrialOut(n_cw, N)
+    rc = L.ldpc_dna_trial_host(dna_llr._p(k), n_cw, N, None if cw is None else dna_llr._p(cw),
+                               dna_llr.TRIAL_DECODE_FN(cb), None, float(eps), int(max_iter), int(bool(faithful)),
+                               out.ref())
+    if raised:
+        raise raised[0]
+    mod._check(rc)
+    return out.result()
+
+
+class ResidentTrial:
+    """A trial whose decoder input stays on the GPU (ldpc_trial_*, DESIGN.md
+    sec. 8.8): one engine, the true codewords, the int8 code matrix and the
+    buffers of both decodes live in the handle and are reused by every run.
+    codewords None: genie-less (a codeword fails iff its syndrome at exit is
+    not zero; error counts read -1).
+
+        T = ResidentTrial(graph, codewords)
+        res = T.run_raw((seqs, quals))          # keys of trial_from_raw_reads(native=True)
+        res = T.run_codes(codes)                # keys of decode_trial
+        print(report(res))
+
+    The times in the result (t_llr_s, t_first_s, t_second_s) are the library's
+    own, returned in ldpc_trial_result."""
+
+    def __init__(self, graph, codewords: Optional[np.ndarray] = None, algo="bp", device: int = 0,
+                 n_cw: Optional[int] = None, schedule=None):
+        import ctypes as C
+
+        import dna_llr
+        import ldpc_amd
+        self._mod, self._L = dna_llr._lib()
+        self.graph, self.device, self.algo = graph, device, ldpc_amd._algo(algo)
+        self.codewords = None
+        if codewords is not None:
+            self.codewords = np.ascontiguousarray(codewords, np.uint8)
+            if self.codewords.ndim != 2 or self.codewords.shape[1] != graph.N:
+                raise ValueError(f"codewords must have shape [n_cw][{graph.N}]")
+            if n_cw is not None and n_cw != len(self.codewords):
+                raise ValueError("n_cw differs from the number of codewords")
+            n_cw = len(self.codewords)
+        self.n_cw = int(2 * dna_llr.PAYLOAD_NT if n_cw is None else n_cw)
+        self.N = graph.N
+        sch = ldpc_amd._schedule(schedule)
+        err = C.c_int(0)
+        self._h = self._L.ldpc_trial_create(graph.handle, device, self.algo, self.n_cw,
+                                            None if self.codewords is None else dna_llr._p(self.codewords),
+                                            None if sch is None else C.byref(sch), C.byref(err))
+        if not self._h:
+            raise ldpc_amd.LdpcError(err.value, (self._L.ldpc_last_error() or b"").decode(errors="replace"))
+
+    def run_codes(self, codes: np.ndarray, eps: float = 0.02, max_iter: int = 200, faithful: bool = True) -> Dict:
+        """The trial of int8 codes [B][N], B <= n_cw, against the first B
+        codewords: decode_trial(table[codes + 128], codewords[:B], codes=codes)."""
+        import dna_llr
+        k = np.ascontiguousarray(codes)
+        if k.dtype != np.int8 or k.ndim != 2 or k.shape[1] != self.N:
+            raise ValueError(f"codes must be int8 [B][{self.N}]")
+        out = _TrialOut(max(len(k), 1), self.N)
+        self._mod._check(self._L.ldpc_trial_run_codes(self._h, dna_llr._p(k), len(k), float(eps), int(max_iter),
+                                                      int(bool(faithful)), out.ref()))
+        return out.result()
+
+    def _run_reads(self, index_vals, seqs, quals, eps, max_iter, align_fn, faithful, workspace_bytes):
+        """ldpc_trial_run_reads -> the result dict, or None when the codes cannot carry the input."""
+        import dna_llr
+        mod, L = self._mod, self._L
+        buf, offs, lens, q, iv, sidx, n = dna_llr._native_inputs(index_vals, seqs, quals, None)
+        out = _TrialOut(self.n_cw, self.N, n_strands=len(sidx))
+        p = dna_llr._p
+        rc = L.ldpc_trial_run_reads(self._h, p(buf), p(offs), p(lens), p(q), n, None if iv is None else p(iv), p(sidx),
+                                    len(sidx), dna_llr.PAYLOAD_NT, 1 if dna_llr._native_align(align_fn) else 0,
+                                    int(workspace_bytes), float(eps), int(max_iter), int(bool(faithful)), out.ref())
+        if rc == mod.LDPC_ERR_UNSUPPORTED and out.r.codes_exact == 0 and self.codewords is not None:
+            return None
+        dna_llr._native_check(mod, rc)
+        res = out.result()
+        kind, stats = out.a["kind"], out.a["stats"]
+        res.update(t_llr_s=out.r.t_llr_s, n_erased_strands=int((kind == dna_llr.KIND_NONE).sum()),
+                   n_reads_valid=int(stats[0]), n_align_pairs=int(stats[3]), t_align_s=0.0, llr=None, resident=True,
+                   kind=kind, stats=stats)
+        return res
+
+    def _fallback_fn(self):
+        return gpu_decode_fn(self.graph, {0: "bp", 1: "msa"}[int(self.algo)])
+
+    def run_reads(self, reads, eps: float = 0.02, max_iter: int = 200, align_fn="star", faithful: bool = True,
+                  workspace_bytes: int = 0) -> Dict:
+        """run_raw for reads whose index is decoded already: reads = (index
+        values, payloads, qualities); the keys of trial_from_reads(native=True)."""
+        res = self._run_reads(*reads, eps, max_iter, align_fn, faithful, workspace_bytes)
+        if res is None:
+            res = trial_from_reads(reads, self.codewords, eps=eps, max_iter=max_iter, align_fn=align_fn,
+                                   decode_fn=self._fallback_fn(), faithful=faithful, device=self.device, native=True)
+            res["resident"] = False
+        return res
+
+    def run_raw(self, raw_reads, eps: float = 0.02, max_iter: int = 200, align_fn="star", faithful: bool = True,
+                workspace_bytes: int = 0) -> Dict:
+        """Raw reads (sequences -- a list of str or a packed (buf, offsets,
+        lengths) triple -- and qualities) to the trial's result in one library
+        call.  The keys are those of trial_from_raw_reads(native=True), with
+        llr None (no LLR matrix is made) and resident=True, plus kind, stats,
+        iters and valid.  When a count difference is outside int8 the codes
+        cannot carry the input (LDPC_ERR_UNSUPPORTED): the call falls back to
+        trial_from_raw_reads(native=True) and marks resident=False (that path
+        needs the true codewords; without them the error is raised)."""
+        seqs, quals = raw_reads
+        res = self._run_reads(None, seqs, quals, eps, max_iter, align_fn, faithful, workspace_bytes)
+        if res is None:
+            res = trial_from_raw_reads(raw_reads, self.codewords, eps=eps, max_iter=max_iter, align_fn=align_fn,
+                                       decode_fn=self._fallback_fn(), faithful=faithful, device=self.device,
+                                       native=True)
+            res["resident"] = False
+            return res
+        hist = {k: int(res["stats"][6 + k]) for k in (-1, 0, 1, 2)}
+        res.update(t_index_s=0.0, n_reads_dropped=hist[-1], cnumerr_hist=hist)
+        return res
+
+    def codes(self, B: Optional[int] = None) -> np.ndarray:
+        """The handle's code matrix after a run, rows [0, B) (ldpc_trial_read_codes)."""
+        import dna_llr
+        B = self.n_cw if B is None else int(B)
+        k = np.zeros((B, self.N), np.int8)
+        self._mod._check(self._L.ldpc_trial_read_codes(self._h, dna_llr._p(k), B))
+        return k
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ldpc_trial_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def report(res: Dict, rs: int = 72000, total_time: Optional[float] = None, threshold: Optional[int] = None,

@@ -141,6 +141,8 @@ EXPORTS = [
     "ldpc_dna_index_encode", "ldpc_dna_index_decode_host", "ldpc_dna_index_decode", "ldpc_dna_strands_host",
     "ldpc_dna_strands", "ldpc_dna_star_align_host", "ldpc_dna_star_align",
     "ldpc_dna_plan_host", "ldpc_dna_plan", "ldpc_dna_reads_llr",
+    "ldpc_dna_trial_host", "ldpc_trial_create", "ldpc_trial_free", "ldpc_trial_run_reads", "ldpc_trial_run_codes",
+    "ldpc_trial_read_codes",
 ]
 
 

@@ -561,6 +561,105 @@ int ldpc_dna_reads_llr(const uint8_t *seqs, const int64_t *offsets, const int32_
                        double *llr, uint8_t *int_mask, int8_t *codes, int32_t *codes_exact, int32_t *kind,
                        int64_t *stats);
 
+/* ------------------------------------------------------------------------ */
+/* A whole DNA trial (decoder.py:541-664, what            */
+/* dna_pipeline.decode_trial does in Python)                                  */
+/* ------------------------------------------------------------------------ */
+/* The decoder input of a trial is one int8 matrix codes [n_cw][N] of count
+ * differences (ldpc_dna_llr_codes); row i's LLRs are table[codes + 128].
+ *
+ *   first decode   every row with table[k + 128] = k * unit, unit =
+ *                  log((1 - eps) / eps); errors[i] = number of hard != truth;
+ *                  fail_first = the rows with errors, 1-based, ascending;
+ *                  re_decode[j] = rows with hard[i][j] != (codes[i][j] < 0);
+ *                  erasure_index = the columns with re_decode > 140, computed
+ *                  once, after the first decode
+ *   second decode  eps2 = eps - 0.0005; while failures remain and eps2 > 0.001:
+ *                  the failed rows are decoded from the same codes with
+ *                  table[k + 128] = (k == 0) ? 0 : ((k * unit) * num) / den,
+ *                  num = log((1 - eps2 + 0.0005) / (eps2 - 0.0005)), den = unit
+ *                  (the reference's rescale of the LLRs, in its operation
+ *                  order), then eps2 -= 0.0005; a row decoded without errors
+ *                  replaces its row of hard.  faithful != 0 keeps the
+ *                  reference's reset of the failure list per codeword
+ *                  (decoder.py:659-661: only the last re-decoded row's outcome
+ *                  survives an iteration), faithful = 0 tracks every failure
+ *   genie-less     without the true codewords (codewords = NULL) a row fails
+ *                  iff its valid flag (syndrome at exit) is 0; its error count
+ *                  reads -1, and 0 for a row that did not fail
+ *
+ * ldpc_trial_result: counts, and caller-owned arrays any of which may be NULL.
+ * fail_first / fail_second / first_errors / second_errors / iters / valid hold
+ * n_cw entries (the lists' lengths are n_fail_first / n_fail_second;
+ * second_errors is -2 for a row that was never re-decoded), erasure_index N
+ * (n_erasure used), hard [n_cw][N] (the first decode's bits with the second
+ * decode's replacements), iters / valid of the first decode, kind [n_strands]
+ * and stats[9] as ldpc_dna_plan (ldpc_trial_run_reads only), codes_exact as
+ * ldpc_dna_llr_codes.  t_llr_s / t_first_s / t_second_s: seconds the library
+ * spent in the planner + code kernel, the first decode with its statistics,
+ * and the second-decode loop. */
+typedef struct ldpc_trial_result {
+    int32_t n, first_success, second_success, second_iterations;
+    int32_t n_fail_first, n_fail_second, n_erasure, codes_exact;
+    int32_t *fail_first, *fail_second;
+    int32_t *first_errors, *second_errors;
+    int32_t *erasure_index;
+    uint8_t *hard;
+    int32_t *iters;
+    uint8_t *valid;
+    int32_t *kind;
+    int64_t *stats;
+    double t_llr_s, t_first_s, t_second_s;
+} ldpc_trial_result;
+
+/* The decoder of ldpc_dna_trial_host: decode B rows codes [B][N] as the LLRs
+ * table[codes + 128] with max_iter iterations into hard [B][N] and valid [B]
+ * (1 = zero syndrome at exit).  Nonzero return: the trial ends with it. */
+typedef int (*ldpc_trial_decode_fn)(void *user, const int8_t *codes, const double *table, int64_t B,
+                                    int32_t max_iter, uint8_t *hard, uint8_t *valid);
+
+/* The trial's control flow on host buffers with the caller's decoder (the
+ * library has no CPU decoder): codes [n_cw][N], codewords [n_cw][N] or NULL.
+ * iters of *out is not written.  Null codes / decode / out, n_cw or N < 1,
+ * eps outside (0.0015, 0.5) and max_iter < 0 are LDPC_ERR_ARG. */
+int ldpc_dna_trial_host(const int8_t *codes, int32_t n_cw, int32_t N, const uint8_t *codewords,
+                        ldpc_trial_decode_fn decode, void *user, double eps, int32_t max_iter, int32_t faithful,
+                        ldpc_trial_result *out);
+
+/* The trial handle: one engine (algo LDPC_ALGO_BP or LDPC_ALGO_MSA, its lane
+ * pool sized as ldpc_decode_codes sizes it for n_cw codewords), the true
+ * codewords [n_cw][N] on `device` (NULL: genie-less), the device code matrix
+ * and the buffers of both decodes, created once and reused by every run.  The
+ * decoder input never leaves the device: per stage the host reads errors,
+ * valid and re_decode, at the end the caller's optional hard / iters.  The
+ * graph must outlive the handle; a handle serves one thread at a time.
+ * Without a GPU, good arguments give LDPC_ERR_DEVICE; argument errors are
+ * reported before any device call. */
+typedef struct ldpc_trial ldpc_trial;
+ldpc_trial *ldpc_trial_create(const ldpc_graph *g, int32_t device, int32_t algo, int32_t n_cw,
+                              const uint8_t *codewords, const ldpc_schedule *schedule, int *err);
+void ldpc_trial_free(ldpc_trial *t);
+
+/* Raw reads to trial result: ldpc_dna_plan's planner (arguments as there),
+ * the code kernel straight into the handle's code matrix, then the trial.
+ * Needs 2 * payload_nt == n_cw and n_strands == N (else LDPC_ERR_ARG).  When
+ * some count difference is outside int8 the codes cannot carry the input: the
+ * call writes codes_exact = 0 (kind and stats are filled) and returns
+ * LDPC_ERR_UNSUPPORTED; ldpc_dna_reads_llr and the fp64 decode remain. */
+int ldpc_trial_run_reads(ldpc_trial *t, const uint8_t *seqs, const int64_t *offsets, const int32_t *lengths,
+                         const int32_t *quals, int64_t n_reads, const int32_t *index_vals, const int32_t *strands,
+                         int32_t n_strands, int32_t payload_nt, int32_t align, int64_t workspace_bytes, double eps,
+                         int32_t max_iter, int32_t faithful, ldpc_trial_result *out);
+
+/* The trial of host codes [B][N], 1 <= B <= n_cw, against the first B true
+ * codewords: one upload, then as above. */
+int ldpc_trial_run_codes(ldpc_trial *t, const int8_t *codes, int64_t B, double eps, int32_t max_iter,
+                         int32_t faithful, ldpc_trial_result *out);
+
+/* The handle's code matrix after a run, rows [0, B) to host codes [B][N]
+ * (tests: the code kernel against ldpc_dna_reads_llr's codes). */
+int ldpc_trial_read_codes(ldpc_trial *t, int8_t *codes, int64_t B);
+
 /* Write soft<rs>_n18432_m1860_<i+1>.txt, i < n_files, into dir: row i of
  * llr as str(value)+' ' tokens (decoder.py:511-516, def_func.py:54-57);
  * int_mask (may be NULL) marks the int-0 entries.  Host only. */
