@@ -144,6 +144,26 @@ int main(int argc, char** argv)
         s.pool_tiles = 2;
         show("reg4x32 bp pool_tiles=2", g, LDPC_ALGO_BP, 0, s);
     }
+    // Regular on one side only: a specialised kernel next to a generic one
+    // (rows of degree 72 with other columns, columns of degree 8 with other rows).
+    const auto mixed = [](const char* name, const HostGraph& g) {
+        std::printf("%s: M=%d N=%d E=%lld dc=%d dv=%d regular=%d%d pool_tiles=%d\n", name, g.M, g.N, (long long)g.E,
+                    g.dc_max, g.dv_max, g.regular_dc, g.regular_dv, gen_pool_tiles(g));
+        const ldpc_schedule res = sched(LDPC_SCHED_RESIDENT, LDPC_SCHED_RESIDENT);
+        const std::string n(name);
+        show((n + " bp").c_str(), g, LDPC_ALGO_BP, 0, sched());
+        show((n + " msa").c_str(), g, LDPC_ALGO_MSA, 0, sched());
+        show((n + " bp resident").c_str(), g, LDPC_ALGO_BP, 0, res);
+        show((n + " msa resident").c_str(), g, LDPC_ALGO_MSA, 0, res);
+    };
+    {
+        const HostGraph g = regular_graph(5, 6, 72);  // N = 360: 32 does not divide it
+        mixed("reg6x72", g);
+        show("reg6x72 bp chunk=320", g, LDPC_ALGO_BP, 320, sched());
+        show("reg6x72 bp chunk=320 resident", g, LDPC_ALGO_BP, 320, sched(LDPC_SCHED_RESIDENT, LDPC_SCHED_RESIDENT));
+    }
+    mixed("reg8x48", regular_graph(5, 8, 48));    // N = 240
+    mixed("reg8x100", regular_graph(3, 8, 100));  // N = 300: rows past the last check bucket
 
     show_sched("null", ldpc_schedule{});
     show_sched("unknown bits", sched(0x7fffffff, 0x7fffffff & ~LDPC_SCHED_RESIDENT));

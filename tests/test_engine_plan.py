@@ -72,6 +72,36 @@ EXPECTED = {
     "reg4x32 bp": _plan(res=1, cap=64 * 43),
     "reg4x32 msa": _plan(res=1, cap=64 * 43),
     "reg4x32 bp pool_tiles=2": _plan(res=1, cap=128),
+    # Regular on one side only (a specialised kernel next to a generic one).  None is (8, 72)-regular, so
+    # no compressed min-sum, hand-over or first check from the prior, and the resident pool comes from
+    # gen_res alone (both degrees in a register bucket), which puts no condition on N.
+    # (6, 72)-regular, N = 360 (N % 32 = 8): rows in check bucket 96, columns in variable bucket 8 -> resident;
+    # E = 30 x 72 = 2160, pool of floor(226e6 / (512 x (2160 + 360))) = floor(226e6 / 1290240) = 175 tiles
+    "reg6x72": "M=30 N=360 E=2160 dc=72 dv=6 regular=11 pool_tiles=175",
+    "reg6x72 bp": _plan(res=1, cap=64 * 175),
+    "reg6x72 msa": _plan(res=1, cap=64 * 175),
+    "reg6x72 bp resident": _plan(res=1, cap=64 * 175),
+    "reg6x72 msa resident": _plan(res=1, cap=64 * 175),
+    # an explicit pool of 5 tiles > kResAutoMaxTiles = 4: grouped unless the caller chose RESIDENT;
+    # scratch max(3, (5 + 3) / 4) = 3 tiles of 64 x 2160 fp64
+    "reg6x72 bp chunk=320": _plan(cap=320, group=3, c2v_tiles=3, c2v_bytes=3 * 64 * 2160 * 8),
+    "reg6x72 bp chunk=320 resident": _plan(res=1, cap=320),
+    # (8, 48)-regular, N = 240: continuous by its columns (degree 8), check bucket 48 -> resident;
+    # E = 40 x 48 = 1920, floor(226e6 / (512 x (1920 + 240))) = floor(226e6 / 1105920) = 204 tiles
+    "reg8x48": "M=40 N=240 E=1920 dc=48 dv=8 regular=11 pool_tiles=204",
+    "reg8x48 bp": _plan(res=1, cap=64 * 204),
+    "reg8x48 msa": _plan(res=1, cap=64 * 204),
+    "reg8x48 bp resident": _plan(res=1, cap=64 * 204),
+    "reg8x48 msa resident": _plan(res=1, cap=64 * 204),
+    # (8, 100)-regular, N = 300: rows past the last check bucket (96), so never resident, whatever the
+    # caller sets: the grouped schedule over 16384 lanes = 256 tiles, groups of 3, scratch
+    # max(3, (256 + 3) / 4) = 64 tiles of 64 x E fp64, E = 24 x 100 = 2400;
+    # gen_pool_tiles (not used): floor(226e6 / (512 x (2400 + 300))) = floor(226e6 / 1382400) = 163
+    "reg8x100": "M=24 N=300 E=2400 dc=100 dv=8 regular=11 pool_tiles=163",
+    "reg8x100 bp": _plan(cap=16384, group=3, c2v_tiles=64, c2v_bytes=64 * 64 * 2400 * 8),
+    "reg8x100 msa": _plan(cap=16384, group=3, c2v_tiles=64, c2v_bytes=64 * 64 * 2400 * 8),
+    "reg8x100 bp resident": _plan(cap=16384, group=3, c2v_tiles=64, c2v_bytes=64 * 64 * 2400 * 8),
+    "reg8x100 msa resident": _plan(cap=16384, group=3, c2v_tiles=64, c2v_bytes=64 * 64 * 2400 * 8),
     # resolve_schedule.  All known bits 0xf0b9, the defaults 0x30b9 (the two debug bits off); bit 30 marks
     # a resolved schedule, bit 29 a caller that chose RESIDENT itself
     "null": "set=0x4000f0b9 flags=0x30b9 group=-2 cpw=-2 pool=0 poll=8 syn=32 reserved=0",
