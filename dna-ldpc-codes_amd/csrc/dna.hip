@@ -35,7 +35,9 @@
 // The step after it, the trial loop of decoder.py:541-664 with the decoder
 // input kept on the device (dna_trial.hpp): the kernels,
 // the handle and the ldpc_trial_* entry points are dna_trial_kernels.hpp,
-// included last.
+// included last.  The step before all of it, strands -> raw reads through a
+// counter-hashed substitution / insertion / deletion channel (dna_sim.hpp,
+// DESIGN.md sec. 8.9): dna_sim_kernels.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,6 +49,7 @@
 #include "../../include/ldpc_amd.h"
 #include "engine.hpp"
 #include "dna_plan.hpp"
+#include "dna_sim.hpp"
 #include "dna_trial.hpp"
 #include "host_decode.hpp"  // ldpc_graph
 #include "rs_index.hpp"
@@ -1136,6 +1139,9 @@ int ldpc_dna_reads_llr(const uint8_t* seqs, const int64_t* offsets, const int32_
 }
 
 }  // extern "C"
+
+// --- the sequencing channel (dna_sim.hpp) ---------------
+#include "dna_sim_kernels.hpp"
 
 // --- the trial handle (dna_trial.hpp) -------------------
 #include "dna_trial_kernels.hpp"

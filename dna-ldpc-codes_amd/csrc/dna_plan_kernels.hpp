@@ -21,6 +21,10 @@
 //   k_plan_close       reads with a partner at distance < 15
 //   k_plan_cand_count / k_plan_cand_fill   the candidate list of every ragged
 //                      strand: the aligner's groups, group s = strand s
+//   k_plan_check_src / k_plan_cand_len / k_plan_cand_gather   only when the reads
+//                      are device-resident already (PlanSrc):
+//                      the range check of the reads, and the candidates packed
+//                      for the one copy down the aligner's host merge needs
 //   star_align_device  (dna.hip) on the resident reads; the merge is host code
 //   k_plan_rows        one wave per row: rows, row_q, the kinds of aligned strands
 #pragma once
@@ -378,14 +382,86 @@ struct PlanDev {
     int64_t R = 0;
 };
 
+// Reads that are on the device already (the sequencing channel's, DESIGN.md
+// sec. 8.9), in place of the four uploads: seqs holds seq_bytes bytes, the
+// arrays n_reads entries.  `bad` (may be null) is the producer's flag word.
+struct PlanSrc {
+    const uint8_t* seqs;
+    const int64_t* offsets;
+    const int32_t* lengths;
+    const int32_t* quals;
+    int64_t seq_bytes;
+    const int32_t* bad;
+};
+
+// The check of device-resident reads that plan::check_args makes of host ones:
+// every read inside seqs.  Also folds the producer's flag word in.
+__global__ void __launch_bounds__(256) k_plan_check_src(const int64_t* __restrict__ off, const int32_t* __restrict__ len,
+                                                        int64_t n, int64_t seq_bytes, const int32_t* __restrict__ src_bad,
+                                                        PlanCtl* __restrict__ ctl)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0 && src_bad && *src_bad) ctl->bad = 1;
+    if (i >= n) return;
+    const int64_t o = off[i], l = len[i];
+    if (l < 0 || o < 0 || o > seq_bytes || l > seq_bytes - o) ctl->bad = 1;
+}
+
+// Candidate c of device-resident reads: its payload length (the read's bytes
+// from `skip` on), 0 and the flag when the read id or the length fails its check.
+__global__ void __launch_bounds__(256) k_plan_cand_len(const int32_t* __restrict__ cand_ids, int64_t C, int64_t n,
+                                                       const int32_t* __restrict__ len, int32_t skip,
+                                                       int32_t* __restrict__ clen, PlanCtl* __restrict__ ctl)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const int32_t id = cand_ids[c];
+    int32_t l = 0;
+    if (id < 0 || id >= n || len[id] < skip || len[id] - skip > kPlanMaxLen) ctl->bad = 1;
+    else l = len[id] - skip;
+    clen[c] = l;
+}
+
+// One wave per candidate (4 per block): its payload bytes, packed at coff[c]
+// of a buffer of T = coff[C] bytes.  The source range was checked by
+// k_plan_check_src, the id and length by k_plan_cand_len (clen is its output);
+// both are checked again here, with the destination range.
+__global__ void __launch_bounds__(256) k_plan_cand_gather(const int32_t* __restrict__ cand_ids, int64_t C, int64_t n,
+                                                          const uint8_t* __restrict__ seqs,
+                                                          const int64_t* __restrict__ off, int64_t seq_bytes,
+                                                          int32_t skip, const int64_t* __restrict__ coff,
+                                                          const int32_t* __restrict__ clen, int64_t T,
+                                                          uint8_t* __restrict__ out, PlanCtl* __restrict__ ctl)
+{
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= C) return;
+    const int32_t id = cand_ids[c];
+    if (id < 0 || id >= n) {
+        if (lane == 0) ctl->bad = 1;
+        return;
+    }
+    const int64_t o = off[id], d = coff[c], l = clen[c];
+    if (l < 0 || o < 0 || o > seq_bytes - skip - l || d < 0 || d > T - l) {
+        if (lane == 0) ctl->bad = 1;
+        return;
+    }
+    for (int64_t j = lane; j < l; j += 64) out[d + j] = seqs[o + skip + j];
+}
+
 // The device planner.  Host outputs of `a` that are null are skipped (the
-// fused call passes none but kind / stats).
+// fused call passes none but kind / stats).  With `src` the reads are the
+// device-resident ones (a.seqs / offsets / lengths / quals are not read): the
+// aligner's merge, the one host consumer of read bytes, gets the candidates
+// packed by k_plan_cand_gather and copied down, nothing else crosses.
 int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, int32_t device,
-                int64_t workspace_bytes, PlanDev* pd)
+                int64_t workspace_bytes, PlanDev* pd, const PlanSrc* src = nullptr)
 {
     int64_t total = 0;
     {
-        const std::string err = plan::check_args(a, &total, host_outputs);
+        plan::Args host = a;
+        if (src && host.n_reads > 0) host.n_reads = 0;  // no host reads to check
+        const std::string err = plan::check_args(host, &total, host_outputs);
         if (!err.empty()) {
             set_error(who + ": " + err);
             return LDPC_ERR_ARG;
@@ -415,23 +491,44 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
     dev_ptr<int32_t> dlen, dq, dstr, div, dne, dpos, dplen, dcnt, dtmp, dids, dslen;
     dev_ptr<PlanCtl> dctl;
     int rc;
-    if ((rc = upload(dseq, a.seqs, (size_t)total))) return rc;
-    if ((rc = upload(doff, a.offsets, (size_t)n))) return rc;
-    if ((rc = upload(dlen, a.lengths, (size_t)n))) return rc;
-    if ((rc = upload(dq, a.quals, (size_t)n))) return rc;
+    if (!src) {
+        if ((rc = upload(dseq, a.seqs, (size_t)total))) return rc;
+        if ((rc = upload(doff, a.offsets, (size_t)n))) return rc;
+        if ((rc = upload(dlen, a.lengths, (size_t)n))) return rc;
+        if ((rc = upload(dq, a.quals, (size_t)n))) return rc;
+    }
+    const uint8_t* d_seq = src ? src->seqs : dseq.get();
+    const int64_t* d_off = src ? src->offsets : doff.get();
+    const int32_t* d_len = src ? src->lengths : dlen.get();
+    const int32_t* d_q = src ? src->quals : dq.get();
     if ((rc = upload(dstr, a.strands, SS))) return rc;
     PlanCtl ctl{};
     ctl.long_read = INT32_MAX;
     ctl.empty_strand = INT32_MAX;
     if ((rc = upload(dctl, &ctl, 1))) return rc;
+    if (src) {  // before any kernel follows an offset
+        if (src->seq_bytes < 0 || (n > 0 && (!src->seqs || !src->offsets || !src->lengths || !src->quals))) {
+            set_error(who + ": bad device-resident reads");
+            return LDPC_ERR_ARG;
+        }
+        int32_t bad = 0;
+        hipLaunchKernelGGL(k_plan_check_src, dim3(plan_blocks(n, 256)), dim3(256), 0, 0, d_off, d_len, n,
+                           src->seq_bytes, src->bad, dctl.get());
+        LDPC_HIP(hipGetLastError());
+        LDPC_HIP(hipMemcpy(&bad, &dctl.get()->bad, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad) {
+            set_error(who + ": the device-resident reads failed their range check");
+            return LDPC_ERR_DEVICE;
+        }
+    }
     if (a.index_vals) {
         if ((rc = upload(div, a.index_vals, (size_t)n))) return rc;
     } else {
         if ((rc = dev_alloc(div, nn))) return rc;
         if ((rc = dev_alloc(dne, nn))) return rc;
         if (n > 0) {
-            hipLaunchKernelGGL(k_rs_index_decode, dim3(plan_blocks(n, 256)), dim3(256), 0, 0, dseq.get(),
-                               doff.get(), dlen.get(), n, div.get(), dne.get());
+            hipLaunchKernelGGL(k_rs_index_decode, dim3(plan_blocks(n, 256)), dim3(256), 0, 0, d_seq,
+                               d_off, d_len, n, div.get(), dne.get());
             LDPC_HIP(hipGetLastError());
         }
     }
@@ -460,7 +557,7 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
 
     if (n > 0) {
         hipLaunchKernelGGL(k_plan_locate, per_read, b256, 0, 0, div.get(),
-                           a.index_vals ? nullptr : dne.get(), doff.get(), dlen.get(), n,
+                           a.index_vals ? nullptr : dne.get(), d_off, d_len, n,
                            dstr.get(), S, nt, dpos.get(), dpoff.get(), dplen.get(),
                            d_cnt, d_notfull, d_ctl);
         LDPC_HIP(hipGetLastError());
@@ -478,7 +575,7 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
                        dsoff.get(), dslen.get(), d_ctl);
     LDPC_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_plan_classify, per_strand, b256, 0, 0, dstart.get(), S, n, d_notfull,
-                       dids.get(), dslen.get(), dq.get(), nt, pd->kind.get(),
+                       dids.get(), dslen.get(), d_q, nt, pd->kind.get(),
                        dnp.get(), drc.get(), d_ctl);
     LDPC_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_plan_scan<int64_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, dnp.get(), (int64_t)S,
@@ -520,7 +617,7 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
         hipLaunchKernelGGL(k_plan_pairs, dim3(plan_blocks(P, 256)), b256, 0, 0, dpstart.get(),
                            dstart.get(), S, n_valid, P, dpa.get(), dpb.get(), d_ctl);
         LDPC_HIP(hipGetLastError());
-        if ((rc = launch_edit_distance(dseq.get(), dsoff.get(), dslen.get(), dpa.get(),
+        if ((rc = launch_edit_distance(d_seq, dsoff.get(), dslen.get(), dpa.get(),
                                        dpb.get(), P, std::max(ctl.max_ragged_len, 0), ddist.get())))
             return rc;
         hipLaunchKernelGGL(k_plan_close, dim3(plan_blocks(P, 256)), b256, 0, 0, dpa.get(), dpb.get(),
@@ -566,19 +663,56 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
             set_error(who + ": the device plan is inconsistent");
             return LDPC_ERR_DEVICE;
         }
-        for (int64_t c = 0; c < C; c++) {
-            const int32_t r = cand[(size_t)c];
-            if (r < 0 || r >= n || a.lengths[r] < skip) {
+        std::vector<uint8_t> cseq;     // device source: the candidates' payloads, packed
+        dev_ptr<uint8_t> dcseq;
+        const uint8_t* star_seqs = a.seqs;
+        const uint8_t* d_star_seqs = d_seq;
+        if (!src) {
+            for (int64_t c = 0; c < C; c++) {
+                const int32_t r = cand[(size_t)c];
+                if (r < 0 || r >= n || a.lengths[r] < skip) {
+                    set_error(who + ": the device plan is inconsistent");
+                    return LDPC_ERR_DEVICE;
+                }
+                coff[(size_t)c] = a.offsets[r] + skip;
+                clen[(size_t)c] = (int32_t)(a.lengths[r] - skip);
+            }
+        } else {
+            dev_ptr<int32_t> dclen;
+            dev_ptr<int64_t> dcoff;
+            int64_t T = 0;
+            if ((rc = dev_alloc(dclen, (size_t)C)) || (rc = dev_alloc(dcoff, (size_t)C + 1))) return rc;
+            hipLaunchKernelGGL(k_plan_cand_len, dim3(plan_blocks(C, 256)), b256, 0, 0, dcand.get(), C, n, d_len,
+                               (int32_t)skip, dclen.get(), d_ctl);
+            LDPC_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_plan_scan<int32_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, dclen.get(), C,
+                               dcoff.get());
+            LDPC_HIP(hipGetLastError());
+            LDPC_HIP(hipMemcpy(&T, dcoff.get() + C, sizeof T, hipMemcpyDeviceToHost));
+            if (T < 0 || T > C * (int64_t)kPlanMaxLen) {
                 set_error(who + ": the device plan is inconsistent");
                 return LDPC_ERR_DEVICE;
             }
-            coff[(size_t)c] = a.offsets[r] + skip;
-            clen[(size_t)c] = (int32_t)(a.lengths[r] - skip);
+            if ((rc = dev_alloc(dcseq, (size_t)T))) return rc;
+            hipLaunchKernelGGL(k_plan_cand_gather, dim3(plan_blocks(C, 4)), b256, 0, 0, dcand.get(), C, n, d_seq,
+                               d_off, src->seq_bytes, (int32_t)skip, dcoff.get(), dclen.get(), T, dcseq.get(), d_ctl);
+            LDPC_HIP(hipGetLastError());
+            cseq.resize((size_t)T);
+            LDPC_HIP(hipMemcpy(coff.data(), dcoff.get(), sizeof(int64_t) * (size_t)C, hipMemcpyDeviceToHost));
+            LDPC_HIP(hipMemcpy(clen.data(), dclen.get(), sizeof(int32_t) * (size_t)C, hipMemcpyDeviceToHost));
+            if (T > 0) LDPC_HIP(hipMemcpy(cseq.data(), dcseq.get(), (size_t)T, hipMemcpyDeviceToHost));
+            LDPC_HIP(hipMemcpy(&ctl, dctl.get(), sizeof ctl, hipMemcpyDeviceToHost));
+            if (ctl.bad) {
+                set_error(who + ": the device plan is inconsistent");
+                return LDPC_ERR_DEVICE;
+            }
+            star_seqs = cseq.data();
+            d_star_seqs = dcseq.get();
         }
-        StarCall sc{a.seqs, coff.data(), clen.data(), C, cptr.data(), (int64_t)S, centre.data(), width.data(),
+        StarCall sc{star_seqs, coff.data(), clen.data(), C, cptr.data(), (int64_t)S, centre.data(), width.data(),
                     out_ptr.data(), nullptr, 0, nullptr, nullptr};
         sc.out_vec = &out;
-        if ((rc = star_align_device(sc, device, workspace_bytes, nullptr, who, dseq.get()))) return rc;
+        if ((rc = star_align_device(sc, device, workspace_bytes, nullptr, who, d_star_seqs))) return rc;
         // the rows to upload: the aligned row (width == payload_nt), else its last byte in byte 0
         std::vector<uint8_t> arows((size_t)C * (size_t)nt, star::kGap);
         for (int32_t s = 0; s < S; s++) {
@@ -601,8 +735,8 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
     if (R > 0) {
         hipLaunchKernelGGL(k_plan_rows, dim3((unsigned)std::min<int64_t>((R + 3) / 4, 2048)), b256, 0, 0,
                            pd->row_ptr.get(), S, R, dstart.get(), n_valid, n, dcptr.get(), C,
-                           dcand.get(), darows.get(), dwidth.get(), dseq.get(),
-                           dsoff.get(), dslen.get(), dids.get(), dq.get(), nt,
+                           dcand.get(), darows.get(), dwidth.get(), d_seq,
+                           dsoff.get(), dslen.get(), dids.get(), d_q, nt,
                            pd->kind.get(), pd->rows.get(), pd->row_q.get(), d_ctl);
         LDPC_HIP(hipGetLastError());
     }

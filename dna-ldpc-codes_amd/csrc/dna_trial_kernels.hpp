@@ -9,6 +9,10 @@
 // device memory is range-checked before use; a failed check sets the handle's
 // flag word and the call fails with LDPC_ERR_DEVICE.
 //
+// ldpc_trial_run_sim puts the sequencing channel's kernel
+// (k_sim_reads, dna_sim_kernels.hpp) on the null stream ahead of the planner,
+// which then reads the handle's device-resident reads instead of uploads.
+//
 //   k_dna_codes      k_dna_llr's count rule, int8 codes and the overflow word only
 //   k_trial_stats    one pass over hard, codes and truth: errors per row,
 //                    re_decode per column, integer atomics only
@@ -176,6 +180,14 @@ struct ldpc_trial {
     ldpc::dev_ptr<int32_t> iters, biters, errors, re_decode, rows, pos;
     ldpc::dev_ptr<int32_t> ctl;  // [0] a failed range check, [1] the code kernel's overflow word
     bool batch = false;          // the last decode went to bhard / bvalid
+    // the sequencing channel (ldpc_trial_set_strands / ldpc_trial_run_sim): the strands, uploaded once, and
+    // the reads of the last run, grown on demand and reused
+    int32_t strand_nt = 0;       // 0: no strands set
+    ldpc::dev_ptr<uint8_t> strands, sim_reads;
+    ldpc::dev_ptr<int64_t> sim_off;
+    ldpc::dev_ptr<int32_t> sim_len, sim_q, sim_qval, sim_bad;
+    ldpc::dev_ptr<uint32_t> sim_qlo;
+    size_t sim_cap_reads = 0, sim_cap_bytes = 0;
 
     ~ldpc_trial()
     {
@@ -329,10 +341,10 @@ int trial_run_codes(ldpc_trial* t, const int8_t* codes, int64_t B, double eps, i
     return trial_run(*t, (int32_t)B, eps, max_iter, faithful, out);
 }
 
-int trial_run_reads(ldpc_trial* t, const plan::Args& a, int64_t workspace_bytes, double eps, int32_t max_iter,
-                    int32_t faithful, ldpc_trial_result* out)
+// The argument checks every reads-to-result call shares.
+int trial_reads_args(const ldpc_trial* t, const std::string& who, const plan::Args& a, double eps, int32_t max_iter,
+                     const ldpc_trial_result* out)
 {
-    const std::string who = "ldpc_trial_run_reads";
     if (!t) { set_error(who + ": null handle"); return LDPC_ERR_ARG; }
     const std::string err = trial::check_args(t->n_cw, t->N, eps, max_iter, out);
     if (!err.empty()) { set_error(who + ": " + err); return LDPC_ERR_ARG; }
@@ -340,9 +352,17 @@ int trial_run_reads(ldpc_trial* t, const plan::Args& a, int64_t workspace_bytes,
         set_error(who + ": needs 2 * payload_nt == n_cw and n_strands == N");
         return LDPC_ERR_ARG;
     }
-    const auto t0 = std::chrono::steady_clock::now();
+    return LDPC_OK;
+}
+
+// Planner (reads from the host, or device-resident with `src`), code kernel
+// into the handle's code matrix, trial.  t0: when the call's LLR stage began.
+int trial_plan_run(ldpc_trial* t, const std::string& who, const plan::Args& a, const PlanSrc* src,
+                   std::chrono::steady_clock::time_point t0, int64_t workspace_bytes, double eps, int32_t max_iter,
+                   int32_t faithful, ldpc_trial_result* out)
+{
     PlanDev pd;
-    if (int rc = plan_device(who, a, false, t->device, workspace_bytes, &pd)) return rc;
+    if (int rc = plan_device(who, a, false, t->device, workspace_bytes, &pd, src)) return rc;
     // the planner's kernels ran on the null stream: the engine's stream waits for them
     hipStream_t s = t->eng.stream.get();
     LDPC_HIP(hipEventRecord(t->planned.get(), nullptr));
@@ -363,6 +383,92 @@ int trial_run_reads(ldpc_trial* t, const plan::Args& a, int64_t workspace_bytes,
         return LDPC_ERR_UNSUPPORTED;
     }
     return trial_run(*t, t->n_cw, eps, max_iter, faithful, out);
+}
+
+int trial_run_reads(ldpc_trial* t, const plan::Args& a, int64_t workspace_bytes, double eps, int32_t max_iter,
+                    int32_t faithful, ldpc_trial_result* out)
+{
+    const std::string who = "ldpc_trial_run_reads";
+    if (int rc = trial_reads_args(t, who, a, eps, max_iter, out)) return rc;
+    return trial_plan_run(t, who, a, nullptr, std::chrono::steady_clock::now(), workspace_bytes, eps, max_iter,
+                          faithful, out);
+}
+
+int trial_set_strands(ldpc_trial* t, const uint8_t* strands, int64_t n_strands, int32_t strand_nt)
+{
+    const std::string who = "ldpc_trial_set_strands: ";
+    if (!t) { set_error(who + "null handle"); return LDPC_ERR_ARG; }
+    if (n_strands != t->N || 2 * ((int64_t)strand_nt - rs::kPrefixNt) != t->n_cw) {
+        set_error(who + "needs n_strands == N and 2 * (strand_nt - 16) == n_cw");
+        return LDPC_ERR_ARG;
+    }
+    const std::string err = sim::check_strands(strands, n_strands, strand_nt);
+    if (!err.empty()) { set_error(who + err); return LDPC_ERR_ARG; }
+    LDPC_HIP(hipSetDevice(t->device));
+    int rc;
+    dev_ptr<uint8_t> d;
+    if ((rc = upload(d, strands, (size_t)n_strands * (size_t)strand_nt))) return rc;
+    if (!t->sim_qval && ((rc = dev_alloc(t->sim_qval, (size_t)sim::kMaxQuals)) ||
+                         (rc = dev_alloc(t->sim_qlo, (size_t)sim::kMaxQuals)) || (rc = dev_alloc(t->sim_bad, 1))))
+        return rc;
+    t->strands = std::move(d);
+    t->strand_nt = strand_nt;
+    return LDPC_OK;
+}
+
+struct SimCall {
+    uint64_t seed;
+    int64_t r0, n_reads, t_sub, t_ins, t_del;
+    const int32_t* q_val;
+    const uint32_t* q_lo;
+    int32_t nq;
+};
+
+// The channel's reads of [r0, r0 + n_reads) into the handle's buffers (null
+// stream), then ldpc_trial_run_reads from the planner on with those as its source.
+int trial_run_sim(ldpc_trial* t, const SimCall& c, const int32_t* strand_index_vals, int32_t align,
+                  int64_t workspace_bytes, double eps, int32_t max_iter, int32_t faithful, ldpc_trial_result* out)
+{
+    const std::string who = "ldpc_trial_run_sim";
+    if (!t) { set_error(who + ": null handle"); return LDPC_ERR_ARG; }
+    if (t->strand_nt == 0) { set_error(who + ": no strands set (ldpc_trial_set_strands)"); return LDPC_ERR_ARG; }
+    const plan::Args a{nullptr, nullptr, nullptr, nullptr, c.n_reads, nullptr, strand_index_vals, t->N,
+                       t->strand_nt - rs::kPrefixNt, align, out ? out->kind : nullptr, nullptr, nullptr, nullptr,
+                       out ? out->stats : nullptr};
+    if (int rc = trial_reads_args(t, who, a, eps, max_iter, out)) return rc;
+    const std::string err = sim::check_channel(t->strand_nt, c.r0, c.n_reads, c.t_sub, c.t_ins, c.t_del, c.q_val,
+                                               c.q_lo, c.nq);
+    if (!err.empty()) { set_error(who + ": " + err); return LDPC_ERR_ARG; }
+    if (c.n_reads > INT32_MAX - 1024) {
+        set_error(who + ": too many reads for one call");
+        return LDPC_ERR_UNSUPPORTED;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    LDPC_HIP(hipSetDevice(t->device));
+    const size_t n = (size_t)c.n_reads, bytes = n * (size_t)sim::stride(t->strand_nt);
+    int rc;
+    if (n > t->sim_cap_reads) {
+        t->sim_cap_reads = 0;
+        if ((rc = dev_alloc(t->sim_off, n)) || (rc = dev_alloc(t->sim_len, n)) || (rc = dev_alloc(t->sim_q, n)))
+            return rc;
+        t->sim_cap_reads = n;
+    }
+    if (bytes > t->sim_cap_bytes) {
+        t->sim_cap_bytes = 0;
+        if ((rc = dev_alloc(t->sim_reads, bytes))) return rc;
+        t->sim_cap_bytes = bytes;
+    }
+    LDPC_HIP(hipMemcpy(t->sim_qval.get(), c.q_val, sizeof(int32_t) * (size_t)c.nq, hipMemcpyHostToDevice));
+    LDPC_HIP(hipMemcpy(t->sim_qlo.get(), c.q_lo, sizeof(uint32_t) * (size_t)c.nq, hipMemcpyHostToDevice));
+    LDPC_HIP(hipMemsetAsync(t->sim_bad.get(), 0, sizeof(int32_t), nullptr));
+    if (n > 0 && (rc = launch_sim_reads(t->strands.get(), t->N, t->strand_nt, c.seed, c.r0, c.n_reads, c.t_sub,
+                                        c.t_ins, c.t_del, t->sim_qval.get(), t->sim_qlo.get(), c.nq,
+                                        t->sim_reads.get(), t->sim_off.get(), t->sim_len.get(), t->sim_q.get(),
+                                        nullptr, t->sim_bad.get())))
+        return rc;
+    const PlanSrc src{t->sim_reads.get(), t->sim_off.get(), t->sim_len.get(), t->sim_q.get(), (int64_t)bytes,
+                      t->sim_bad.get()};
+    return trial_plan_run(t, who, a, &src, t0, workspace_bytes, eps, max_iter, faithful, out);
 }
 
 template <class F>
@@ -415,6 +521,23 @@ int ldpc_trial_run_reads(ldpc_trial* t, const uint8_t* seqs, const int64_t* offs
                                                   payload_nt, align, out ? out->kind : nullptr, nullptr, nullptr,
                                                   nullptr, out ? out->stats : nullptr),
                                      workspace_bytes, eps, max_iter, faithful, out);
+    });
+}
+
+int ldpc_trial_set_strands(ldpc_trial* t, const uint8_t* strands, int64_t n_strands, int32_t strand_nt)
+{
+    return ldpc::trial_guard("ldpc_trial_set_strands",
+                             [&] { return ldpc::trial_set_strands(t, strands, n_strands, strand_nt); });
+}
+
+int ldpc_trial_run_sim(ldpc_trial* t, uint64_t seed, int64_t r0, int64_t n_reads, int64_t t_sub, int64_t t_ins,
+                       int64_t t_del, const int32_t* q_val, const uint32_t* q_lo, int32_t nq,
+                       const int32_t* strand_index_vals, int32_t align, int64_t workspace_bytes, double eps,
+                       int32_t max_iter, int32_t faithful, ldpc_trial_result* out)
+{
+    return ldpc::trial_guard("ldpc_trial_run_sim", [&] {
+        return ldpc::trial_run_sim(t, ldpc::SimCall{seed, r0, n_reads, t_sub, t_ins, t_del, q_val, q_lo, nq},
+                                   strand_index_vals, align, workspace_bytes, eps, max_iter, faithful, out);
     });
 }
 

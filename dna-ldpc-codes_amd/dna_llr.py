@@ -168,6 +168,14 @@ def _lib():
                                            pres]
         L.ldpc_trial_run_codes.argtypes = [vp, vp, i64, C.c_double, i32, i32, pres]
         L.ldpc_trial_read_codes.argtypes = [vp, vp, i64]
+        sim = [vp, i32, i32, C.c_uint64, i64, i64, i64, i64, i64, vp, vp, i32, vp, vp, vp, vp]
+        L.ldpc_dna_sim_stride.argtypes = [i32]
+        L.ldpc_dna_sim_stride.restype = i64
+        L.ldpc_dna_sim_reads_host.argtypes = sim
+        L.ldpc_dna_sim_reads.argtypes = sim + [i32]
+        L.ldpc_trial_set_strands.argtypes = [vp, vp, i64, i32]
+        L.ldpc_trial_run_sim.argtypes = [vp, C.c_uint64, i64, i64, i64, i64, i64, vp, vp, i32, vp, i32, i64,
+                                         C.c_double, i32, i32, pres]
         L._dna_bound = True
     return ldpc_amd, L
 

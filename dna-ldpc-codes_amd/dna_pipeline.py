@@ -312,7 +312,8 @@ class ResidentTrial:
             n_cw = len(self.codewords)
         self.n_cw = int(2 * dna_llr.PAYLOAD_NT if n_cw is None else n_cw)
         self.N = graph.N
-        sch = ldpc_amd._schedule(schedule)
+        self.strands = None  # run_sim's, once set
+        sch =ldpc_amd._schedule(schedule)
         err = C.c_int(0)
         self._h = self._L.ldpc_trial_create(graph.handle, device, self.algo, self.n_cw,
                                             None if self.codewords is None else dna_llr._p(self.codewords),
@@ -345,11 +346,24 @@ class ResidentTrial:
         if rc == mod.LDPC_ERR_UNSUPPORTED and out.r.codes_exact == 0 and self.codewords is not None:
             return None
         dna_llr._native_check(mod, rc)
+        return self._resident_result(out)
+
+    @staticmethod
+    def _resident_result(out: "_TrialOut") -> Dict:
+        """The result dict of a reads-to-result call that stayed on the device."""
+        import dna_llr
         res = out.result()
         kind, stats = out.a["kind"], out.a["stats"]
         res.update(t_llr_s=out.r.t_llr_s, n_erased_strands=int((kind == dna_llr.KIND_NONE).sum()),
                    n_reads_valid=int(stats[0]), n_align_pairs=int(stats[3]), t_align_s=0.0, llr=None, resident=True,
                    kind=kind, stats=stats)
+        return res
+
+    @staticmethod
+    def _raw_counts(res: Dict) -> Dict:
+        """The index decoder's keys of a raw-reads result, from the planner's stats."""
+        hist = {k: int(res["stats"][6 + k]) for k in (-1, 0, 1, 2)}
+        res.update(t_index_s=0.0, n_reads_dropped=hist[-1], cnumerr_hist=hist)
         return res
 
     def _fallback_fn(self):
@@ -384,8 +398,55 @@ class ResidentTrial:
                                        native=True)
             res["resident"] = False
             return res
-        hist = {k: int(res["stats"][6 + k]) for k in (-1, 0, 1, 2)}
-        res.update(t_index_s=0.0, n_reads_dropped=hist[-1], cnumerr_hist=hist)
+        return self._raw_counts(res)
+
+    def set_strands(self, strands: np.ndarray) -> None:
+        """The strands run_sim samples, [N][16 + n_cw / 2] uint8 ASCII over ACGT
+        (synth.dna_strands): uploaded once (ldpc_trial_set_strands)."""
+        import dna_llr
+        s = np.ascontiguousarray(strands, np.uint8)
+        if s.ndim != 2:
+            raise ValueError("strands must be uint8 [N][strand_nt]")
+        self._mod._check(self._L.ldpc_trial_set_strands(self._h, dna_llr._p(s), s.shape[0], s.shape[1]))
+        self.strands = s
+
+    def run_sim(self, seed: int, n_reads: int, sub: float = 0.01, ins: float = 0.0, dele: float = 0.0,
+                strands: Optional[np.ndarray] = None, r0: int = 0, quality: Optional[np.ndarray] = None,
+                eps: float = 0.02, max_iter: int = 200, align_fn="star", faithful: bool = True,
+                workspace_bytes: int = 0) -> Dict:
+        """Strands to the trial's result in one library call (ldpc_trial_run_sim,
+        DESIGN.md sec. 8.9): the reads [r0, r0 + n_reads) of the counter-hashed
+        channel (synth.dna_raw_reads_hashed: the same reads) are generated on
+        the GPU and planned, coded and decoded there; the result is
+        run_raw(dna_raw_reads_hashed(...))'s, plus n_reads and seed.  strands:
+        set on the first call and kept -- synth.dna_strands(codewords) by
+        default, which a genie-less handle cannot make (pass them, or call
+        set_strands).  When a count difference is outside int8 the reads are
+        made by the library's host form and go through run_raw's fallback."""
+        import dna_llr
+        import synth
+        mod, L = self._mod, self._L
+        if strands is not None:
+            s = np.ascontiguousarray(strands, np.uint8)
+            if self.strands is None or s.shape != self.strands.shape or (s != self.strands).any():
+                self.set_strands(s)
+        elif self.strands is None and self.codewords is not None:
+            self.set_strands(synth.dna_strands(self.codewords))
+        t_sub, t_ins, t_del, q_val, q_lo = synth.sim_tables(sub, ins, dele, quality)
+        sidx = np.ascontiguousarray(dna_llr.strand_indices(), np.int32)
+        out = _TrialOut(self.n_cw, self.N, n_strands=len(sidx))
+        p = dna_llr._p
+        rc = L.ldpc_trial_run_sim(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(r0), int(n_reads), t_sub, t_ins, t_del,
+                                  p(q_val), p(q_lo), len(q_val), p(sidx), 1 if dna_llr._native_align(align_fn) else 0,
+                                  int(workspace_bytes), float(eps), int(max_iter), int(bool(faithful)), out.ref())
+        if rc == mod.LDPC_ERR_UNSUPPORTED and out.r.codes_exact == 0 and self.codewords is not None:
+            raw = synth.dna_raw_reads_native(self.strands, seed, n_reads, sub, ins, dele, r0=r0, quality=quality)
+            res = self.run_raw(raw, eps=eps, max_iter=max_iter, align_fn=align_fn, faithful=faithful,
+                               workspace_bytes=workspace_bytes)
+        else:
+            dna_llr._native_check(mod, rc)
+            res = self._raw_counts(self._resident_result(out))
+        res.update(n_reads=int(n_reads), seed=int(seed))
         return res
 
     def codes(self, B: Optional[int] = None) -> np.ndarray:
@@ -406,6 +467,28 @@ class ResidentTrial:
             self.close()
         except Exception:
             pass
+
+
+SWEEP_KEYS = ("first_success", "second_success", "second_iterations", "n_erased_strands", "n_reads_valid",
+              "t_llr_s", "t_first_s", "t_second_s")
+
+
+def coverage_sweep(T: ResidentTrial, n_reads_list, trials: int, seed: int = 0, sub: float = 0.01, ins: float = 0.0,
+                   dele: float = 0.0, eps: float = 0.02, max_iter: int = 200, **kw) -> List[Dict]:
+    """At which random-sampling number does the archive still decode: one
+    T.run_sim per read count n of n_reads_list and trial t < trials.  Trial t
+    uses seed `seed + t` and the reads [0, n), so within a trial a smaller
+    count's reads are a prefix of a larger count's.  One row per (n, t), in
+    that order: n_reads, trial, seed, and SWEEP_KEYS of the run's result (the
+    times are the library's own).  Further keywords go to run_sim."""
+    rows = []
+    for n in n_reads_list:
+        for t in range(int(trials)):
+            res = T.run_sim(seed + t, int(n), sub=sub, ins=ins, dele=dele, eps=eps, max_iter=max_iter, **kw)
+            row = {"n_reads": int(n), "trial": t, "seed": seed + t}
+            row.update((k, res[k]) for k in SWEEP_KEYS)
+            rows.append(row)
+    return rows
 
 
 def report(res: Dict, rs: int = 72000, total_time: Optional[float] = None, threshold: Optional[int] = None,

@@ -143,6 +143,8 @@ EXPORTS = [
     "ldpc_dna_plan_host", "ldpc_dna_plan", "ldpc_dna_reads_llr",
     "ldpc_dna_trial_host", "ldpc_trial_create", "ldpc_trial_free", "ldpc_trial_run_reads", "ldpc_trial_run_codes",
     "ldpc_trial_read_codes",
+    "ldpc_dna_sim_stride", "ldpc_dna_sim_reads_host", "ldpc_dna_sim_reads", "ldpc_trial_set_strands",
+    "ldpc_trial_run_sim",
 ]
 
 

@@ -13,6 +13,9 @@
   (kernels.hpp k_gen_bsc) used for configs 3-5; tests check the device output
   against it bit for bit.
 * ``load_codewords`` -- the 272 true codewords (bit-packed fixture).
+* ``dna_raw_reads_hashed`` -- numpy replica of the library's counter-hashed
+  sequencing channel (csrc/dna_sim.hpp, k_sim_reads); ``dna_raw_reads_native``
+  is the library's host / device form, tests hold the three equal byte for byte.
 """
 from __future__ import annotations
 
@@ -242,6 +245,143 @@ def dna_raw_reads(codewords: np.ndarray, seed: int = 0, n_reads: int = 72000, su
                 s.insert(int(rng.integers(0, len(s) + 1)), "ACGT"[int(rng.integers(0, 4))])
             seqs[k] = "".join(s)
     return seqs, quals.tolist()
+
+
+# --- the counter-hashed sequencing channel (csrc/dna_sim.hpp) ---
+SIM_ONE = 1 << 53        # probability 1 as a threshold
+SIM_MAX_STRAND_NT = 399  # a read of 2L + 1 bytes stays within the planner's 800
+
+
+def sim_stride(L: int) -> int:
+    """Bytes between the starts of two reads: 2L + 1 rounded up to a multiple of 16."""
+    return (2 * L + 1 + 15) // 16 * 16
+
+
+def sim_tables(sub: float, ins: float, dele: float, quality: np.ndarray = None):
+    """(t_sub, t_ins, t_del, q_val int32, q_lo uint32): the channel's integer
+    thresholds int(p * 2**53) and its quality table -- the characters with a
+    nonzero count of the histogram (quality_hist() by default), q_lo[i] =
+    (count before i << 32) // total."""
+    t = []
+    for name, p in (("sub", sub), ("ins", ins), ("dele", dele)):
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"{name} must be a probability")
+        t.append(int(p * 2 ** 53))
+    if t[0] + t[2] > SIM_ONE:
+        raise ValueError("sub + dele must not exceed 1")
+    qh = np.asarray(quality_hist() if quality is None else quality).astype(np.int64)
+    q_val = np.nonzero(qh)[0]
+    if qh.ndim != 1 or (qh < 0).any() or not 1 <= len(q_val) <= 256:
+        raise ValueError("the quality histogram needs 1 .. 256 characters with a positive count")
+    counts = [int(c) for c in qh[q_val]]
+    total, before, q_lo = sum(counts), 0, []
+    for c in counts:
+        q_lo.append((before << 32) // total)
+        before += c
+    return t[0], t[1], t[2], np.ascontiguousarray(q_val, np.int32), np.array(q_lo, np.uint32)
+
+
+def _sim_strands(strands) -> np.ndarray:
+    s = np.ascontiguousarray(strands, np.uint8)
+    if s.ndim != 2 or s.shape[0] < 1 or not 1 <= s.shape[1] <= SIM_MAX_STRAND_NT:
+        raise ValueError(f"strands must be uint8 [S][L] with S >= 1 and 1 <= L <= {SIM_MAX_STRAND_NT}")
+    return s
+
+
+def _sim_return(buf, lens, quals, strand_of, stride, with_strands):
+    seqs = (buf.reshape(-1), np.arange(len(lens), dtype=np.int64) * stride, lens)
+    return (seqs, quals, strand_of) if with_strands else (seqs, quals)
+
+
+def dna_raw_reads_hashed(strands: np.ndarray, seed: int, n_reads: int, sub: float = 0.01, ins: float = 0.0,
+                         dele: float = 0.0, r0: int = 0, quality: np.ndarray = None, with_strands: bool = False):
+    """The reads [r0, r0 + n_reads) of the counter-hashed channel over strands
+    [S][L] (ASCII ACGT), in numpy from the definition --
+    the replica the library's host and device forms are held equal to; it does
+    not call the library.  With h(r, c, p) = splitmix64(((r << 24) | (c << 16)
+    | p) ^ splitmix64(seed)), hi = >> 32, u = >> 11: strand (hi(h(r,0,0)) * S)
+    >> 32; quality q_val[largest i with q_lo[i] <= hi(h(r,1,0))]; slot p <= L
+    inserts "ACGT"[(hi(h(r,3,p)) * 4) >> 32] iff u(h(r,2,p)) < t_ins; base p <
+    L, e = u(h(r,4,p)): deleted iff e < t_del, substituted iff e < t_del +
+    t_sub by "ACGT"[(b + 1 + ((hi(h(r,5,p)) * 3) >> 32)) & 3], else copied; the
+    read is insertion p, base p, ..., insertion L.
+
+    Returns (seqs, quals), what ResidentTrial.run_raw takes: seqs the packed
+    triple (buf uint8 [n_reads * stride], offsets int64 = i * stride, lengths
+    int32), bytes beyond a read's length 0; quals int32.  with_strands: a third
+    entry, the strand of every read (int32)."""
+    s = _sim_strands(strands)
+    S, L = s.shape
+    t_sub, t_ins, t_del, q_val, q_lo = sim_tables(sub, ins, dele, quality)
+    if not np.isin(s, _BASES).all():
+        raise ValueError("strands hold a byte outside ACGT")
+    if r0 < 0 or n_reads < 0 or r0 + n_reads > (1 << 40):
+        raise ValueError("the reads must lie in [0, 2^40)")
+    u64 = np.uint64
+    seedmix = _splitmix64(np.array([seed & 0xFFFFFFFFFFFFFFFF], u64))[0]
+    r = np.arange(r0, r0 + n_reads, dtype=u64)
+
+    def h(c, p=None):  # [n] for p None (p = 0), else [n][len(p)]
+        key = (r << u64(24)) | u64(c << 16)
+        if p is not None:
+            key = key[:, None] | p[None, :]
+        return _splitmix64(key ^ seedmix)
+
+    hi = lambda x: x >> u64(32)  # noqa: E731
+    strand_of = ((hi(h(0)) * u64(S)) >> u64(32)).astype(np.int32)
+    quals = q_val[np.searchsorted(q_lo.astype(u64), hi(h(1)), side="right") - 1].astype(np.int32)
+    slots, pos = np.arange(L + 1, dtype=u64), np.arange(L, dtype=u64)
+    ins_on = (h(2, slots) >> u64(11)) < u64(t_ins)
+    ins_base = _BASES[((hi(h(3, slots)) * u64(4)) >> u64(32)).astype(np.int64)]
+    e = h(4, pos) >> u64(11)
+    kept = e >= u64(t_del)
+    subst = kept & (e < u64(t_del + t_sub))
+    src = s[strand_of]
+    b = np.searchsorted(_BASES, src).astype(np.int64)
+    sub_base = _BASES[(b + 1 + ((hi(h(5, pos)) * u64(3)) >> u64(32)).astype(np.int64)) & 3]
+    # columns in output order: slot 0, base 0, slot 1, base 1, ..., slot L
+    cand = np.zeros((n_reads, 2 * L + 1), np.uint8)
+    take = np.zeros((n_reads, 2 * L + 1), bool)
+    cand[:, 0::2], take[:, 0::2] = ins_base, ins_on
+    cand[:, 1::2], take[:, 1::2] = np.where(subst, sub_base, src), kept
+    lens = take.sum(axis=1).astype(np.int32)
+    stride = sim_stride(L)
+    buf = np.zeros((n_reads, stride), np.uint8)
+    rows, cols = np.nonzero(take)
+    buf[rows, (np.cumsum(take, axis=1) - 1)[rows, cols]] = cand[rows, cols]
+    return _sim_return(buf, lens, quals, strand_of, stride, with_strands)
+
+
+def dna_raw_reads_native(strands: np.ndarray, seed: int, n_reads: int, sub: float = 0.01, ins: float = 0.0,
+                         dele: float = 0.0, r0: int = 0, quality: np.ndarray = None, with_strands: bool = False,
+                         device=None):
+    """dna_raw_reads_hashed in the library: ldpc_dna_sim_reads_host on one CPU
+    thread (device None), or ldpc_dna_sim_reads on GPU `device` (k_sim_reads).
+    Same arguments, same return shape, the same bytes up to every read's length."""
+    import dna_llr
+    mod, L = dna_llr._lib()
+    s = _sim_strands(strands)
+    t_sub, t_ins, t_del, q_val, q_lo = sim_tables(sub, ins, dele, quality)
+    return _sim_native(mod, L, s, seed, r0, n_reads, t_sub, t_ins, t_del, q_val, q_lo, with_strands, device)
+
+
+def _sim_native(mod, L, s, seed, r0, n_reads, t_sub, t_ins, t_del, q_val, q_lo, with_strands=False, device=None):
+    """The library call of dna_raw_reads_native on ready tables (tests pass bad ones)."""
+    import ctypes as C
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    S, nt = s.shape
+    stride = int(L.ldpc_dna_sim_stride(nt)) or sim_stride(nt)
+    n = max(int(n_reads), 0)
+    buf = np.zeros((n, stride), np.uint8)
+    lens, quals = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    strand_of = np.zeros(n, np.int32) if with_strands else None
+    args = (p(s), S, nt, C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), int(r0), int(n_reads), int(t_sub), int(t_ins),
+            int(t_del), p(q_val), p(q_lo), 0 if q_val is None else len(q_val), p(buf), p(lens), p(quals), p(strand_of))
+    if device is None:
+        mod._check(L.ldpc_dna_sim_reads_host(*args))
+    else:
+        mod._check(L.ldpc_dna_sim_reads(*args, int(device)))
+    return _sim_return(buf, lens, quals, strand_of, stride, with_strands)
 
 
 def dna_reads_edge_cases(codewords: np.ndarray, reads, seed: int = 1):

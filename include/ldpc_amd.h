@@ -660,6 +660,63 @@ int ldpc_trial_run_codes(ldpc_trial *t, const int8_t *codes, int64_t B, double e
  * (tests: the code kernel against ldpc_dna_reads_llr's codes). */
 int ldpc_trial_read_codes(ldpc_trial *t, int8_t *codes, int64_t B);
 
+/* --- the sequencing channel: strands to raw reads -----
+ *
+ * Strands [n_strands][strand_nt] over ACGT, 1 <= strand_nt <= 399, to the raw
+ * reads [r0, r0 + n_reads) of seed `seed`, r0 + n_reads <= 2^40.  Every draw
+ * is a counter hash, integers only:
+ *   h(r, c, p) = splitmix64(((r << 24) | (c << 16) | p) ^ splitmix64(seed)),
+ *   hi(x) = x >> 32, u(x) = x >> 11;
+ *   strand of read r   (hi(h(r,0,0)) * n_strands) >> 32
+ *   quality            q_val[i], i the largest index with q_lo[i] <= hi(h(r,1,0))
+ *   slot p = 0..L      inserts iff u(h(r,2,p)) < t_ins, the base "ACGT"[(hi(h(r,3,p)) * 4) >> 32]
+ *   base p = 0..L-1    e = u(h(r,4,p)): deleted iff e < t_del; substituted iff
+ *                      t_del <= e < t_del + t_sub by "ACGT"[(b + 1 + ((hi(h(r,5,p)) * 3) >> 32)) & 3]
+ *                      (b: the source base's position in ACGT); else copied
+ *   read               for p = 0..L-1 slot p's insertion, then base p unless
+ *                      deleted; slot L's insertion last: 0 .. 2L + 1 bytes
+ * so a read depends on (seed, r) alone: [0, n1) is a prefix of [0, n2) and a
+ * range split over two calls gives the same bytes.  Thresholds are
+ * probabilities times 2^53, in [0, 2^53] with t_sub + t_del <= 2^53.  The
+ * quality table has 1 <= nq <= 256 entries, q_lo ascending (equal neighbours
+ * allowed) from q_lo[0] = 0: entry i is drawn with probability
+ * (q_lo[i+1] - q_lo[i]) / 2^32.
+ *
+ * Outputs: read r - r0 starts at byte (r - r0) * ldpc_dna_sim_stride(strand_nt)
+ * of `reads` (the stride is 2 * strand_nt + 1 rounded up to a multiple of 16;
+ * 0 for a strand_nt outside 1..399); bytes of a slot beyond the read's length
+ * are unspecified.  lengths / quals [n_reads]; strand_of [n_reads] may be NULL.
+ * With offsets[i] = i * stride this is the planner's input.  Null pointers,
+ * sizes and thresholds outside their ranges, a strand byte outside ACGT and a
+ * descending q_lo are LDPC_ERR_ARG, reported before anything is written.
+ * ldpc_dna_sim_reads_host runs on one CPU thread; ldpc_dna_sim_reads generates
+ * in device memory (one wave per read) and copies down: the same bytes. */
+int64_t ldpc_dna_sim_stride(int32_t strand_nt);
+int ldpc_dna_sim_reads_host(const uint8_t *strands, int32_t n_strands, int32_t strand_nt, uint64_t seed, int64_t r0,
+                            int64_t n_reads, int64_t t_sub, int64_t t_ins, int64_t t_del, const int32_t *q_val,
+                            const uint32_t *q_lo, int32_t nq, uint8_t *reads, int32_t *lengths, int32_t *quals,
+                            int32_t *strand_of);
+int ldpc_dna_sim_reads(const uint8_t *strands, int32_t n_strands, int32_t strand_nt, uint64_t seed, int64_t r0,
+                       int64_t n_reads, int64_t t_sub, int64_t t_ins, int64_t t_del, const int32_t *q_val,
+                       const uint32_t *q_lo, int32_t nq, uint8_t *reads, int32_t *lengths, int32_t *quals,
+                       int32_t *strand_of, int32_t device);
+
+/* The strands a handle's simulated trials sample: uploaded once.  Needs
+ * n_strands == N and 2 * (strand_nt - 16) == n_cw (else LDPC_ERR_ARG). */
+int ldpc_trial_set_strands(ldpc_trial *t, const uint8_t *strands, int64_t n_strands, int32_t strand_nt);
+
+/* Strands to trial result: the channel's reads [r0, r0 + n_reads) generated
+ * into buffers the handle owns (grown on demand, reused), then
+ * ldpc_trial_run_reads from its planner on with those reads as the source --
+ * raw reads, payload_nt = strand_nt - 16, strand_index_vals [N] the planner's
+ * `strands`.  No read crosses to the host but the candidates of ragged
+ * strands, packed, for the aligner's merge.  t_llr_s covers generator +
+ * planner + code kernel.  Without strands set: LDPC_ERR_ARG. */
+int ldpc_trial_run_sim(ldpc_trial *t, uint64_t seed, int64_t r0, int64_t n_reads, int64_t t_sub, int64_t t_ins,
+                       int64_t t_del, const int32_t *q_val, const uint32_t *q_lo, int32_t nq,
+                       const int32_t *strand_index_vals, int32_t align, int64_t workspace_bytes, double eps,
+                       int32_t max_iter, int32_t faithful, ldpc_trial_result *out);
+
 /* Write soft<rs>_n18432_m1860_<i+1>.txt, i < n_files, into dir: row i of
  * llr as str(value)+' ' tokens (decoder.py:511-516, def_func.py:54-57);
  * int_mask (may be NULL) marks the int-0 entries.  Host only. */
