@@ -30,7 +30,10 @@
 //   int keep(const int32_t* rows, const int32_t* pos, int64_t n)
 //       batch rows pos[0..n) of the last decode replace rows rows[pos[q]] of `hard`
 //   bool has_truth()
-// Each returns LDPC_OK or an error code that ends the trial.
+// Each returns LDPC_OK or an error code that ends the trial.  The speculating
+// form of the loop (run_spec, DESIGN.md sec. 8.10: several eps2 steps per
+// decoder call, the control flow replayed over the results) asks for two more
+// operations, described there.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -83,17 +86,62 @@ inline double seconds_since(std::chrono::steady_clock::time_point t0)
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// The eps2 values of the second decodes, by the loop's own subtraction chain
+// (decoder.py:592-611), so the tables and the stop are the loop's.
+inline std::vector<double> eps2_sequence(double eps)
+{
+    std::vector<double> seq;
+    for (double eps2 = eps - kEpsStep; eps2 > kEpsStop; eps2 = eps2 - kEpsStep) seq.push_back(eps2);
+    return seq;
+}
+
+inline int64_t lanes64(int64_t F) { return (F + 63) / 64 * 64; }
+
+// Speculation.  The engine maps one wave to one (row,
+// tile of 64 lanes), so a batch of F rows costs what lanes64(F) rows cost, and
+// the decode of (row, eps2 step) depends on nothing else: the spare lanes hold
+// the same rows under the next steps' tables, and the control flow is replayed
+// over the results.  The codes are small, so several steps' tables fit side by
+// side in the one 256-entry table: with K the largest |code|, W = 2K + 1 and
+// P = 256 / W, step j of a batch has slice [j * W, j * W + W) and its copy of a
+// row carries code + K + j * W - 128.
+//
+// Steps of one decoder call for a list of F rows with `rem` steps left; steps:
+// the caller's setting (-1: as many as fit, n >= 2: at most n).
+inline int64_t spec_steps(int64_t F, int64_t rem, int32_t P, int32_t steps)
+{
+    int64_t k = std::min<int64_t>(std::min<int64_t>(rem, P), lanes64(F) / F);
+    if (steps >= 2) k = std::min<int64_t>(k, steps);
+    return std::max<int64_t>(k, 1);
+}
+
+// T[j * W + (c + K)] = rescale_table(eps, eps2[j])[c + 128] for c in [-K, K], j < k; 0.0 elsewhere
+inline void packed_table(double eps, const double* eps2, int64_t k, int32_t K, double* table)
+{
+    double one[256];
+    const int32_t W = 2 * K + 1;
+    std::fill(table, table + 256, 0.0);
+    for (int64_t j = 0; j < k; j++) {
+        rescale_table(eps, eps2[j], one);
+        for (int32_t c = -K; c <= K; c++) table[j * W + (c + K)] = one[c + 128];
+    }
+}
+
 // One trial over n_cw rows of N columns.  Fills every field of *out but hard,
 // iters, valid (the backend's), kind, stats, codes_exact and t_llr_s (the
-// caller's).  Returns LDPC_OK or the backend's error.
-template <class Backend>
-int run(Backend& be, int32_t n_cw, int32_t N, double eps, int32_t max_iter, bool faithful, ldpc_trial_result* out)
+// caller's).  Returns LDPC_OK or the backend's error.  Spec: the form that may
+// speculate (run_spec below); `steps` and the backend's absmax / decode_spec
+// are used by it alone.  cnt (may be null) gets the counters.
+template <bool Spec, class Backend>
+int run_impl(Backend& be, int32_t n_cw, int32_t N, double eps, int32_t max_iter, bool faithful, int32_t steps,
+             ldpc_trial_result* out, ldpc_trial_counters* cnt)
 {
     const bool genie = be.has_truth();
     std::vector<int32_t> errors((size_t)n_cw), re_decode((size_t)N), second((size_t)n_cw, kNotRedecoded);
     std::vector<uint8_t> valid((size_t)n_cw);
     double table[256];
     int rc;
+    ldpc_trial_counters c{};
 
     auto t0 = std::chrono::steady_clock::now();
     code_table(std::log((1 - eps) / eps), table);
@@ -112,35 +160,68 @@ int run(Backend& be, int32_t n_cw, int32_t N, double eps, int32_t max_iter, bool
             n_erasure++;
         }
 
-    std::vector<int32_t> fail2(fail), next, rows, keep, e2;
+    // The second decodes.  A decoder call covers steps [s, s + k) of the eps2
+    // sequence for the current list (k = 1 unless it speculates): batch row
+    // j * F + f is row fail2[f] under step s + j.  The replay walks the steps
+    // in order; `cur` holds the list's positions f that are still failing.
+    const std::vector<double> seq = eps2_sequence(eps);
+    std::vector<int32_t> fail2(fail), rows, cur, next, keep, e2;
     std::vector<uint8_t> v2;
     int32_t iter_sec = 0;
-    double eps2 = eps - kEpsStep;
+    size_t s = 0;
     t0 = std::chrono::steady_clock::now();
-    while (!fail2.empty() && eps2 > kEpsStop) {
-        iter_sec++;
-        rescale_table(eps, eps2, table);
-        eps2 = eps2 - kEpsStep;
-        const int64_t F = (int64_t)fail2.size();
-        rows.resize((size_t)F);
-        e2.assign((size_t)F, 0);
-        v2.assign((size_t)F, 0);
-        for (int64_t k = 0; k < F; k++) rows[(size_t)k] = fail2[(size_t)k] - 1;
-        if ((rc = be.decode(rows.data(), F, table, max_iter))) return rc;
-        if ((rc = be.stats(rows.data(), F, e2.data(), v2.data(), nullptr))) return rc;
-        next.clear();
-        keep.clear();
-        for (int64_t k = 0; k < F; k++) {
-            const int32_t v = genie ? e2[(size_t)k] : (v2[(size_t)k] ? 0 : -1);
-            second[(size_t)rows[(size_t)k]] = v;
-            if (faithful) next.clear();  // decoder.py:659-661 resets the list per codeword
-            if (v != 0) next.push_back(fail2[(size_t)k]);
-            else keep.push_back((int32_t)k);
+    if constexpr (Spec) {
+        if (steps != 0 && steps != 1 && !fail2.empty() && !seq.empty()) {
+            rows.resize(fail2.size());
+            for (size_t f = 0; f < fail2.size(); f++) rows[f] = fail2[f] - 1;
+            if ((rc = be.absmax(rows.data(), (int64_t)rows.size(), &c.code_absmax))) return rc;
+            c.steps_per_decode = 256 / (2 * c.code_absmax + 1);
         }
+    }
+    while (!fail2.empty() && s < seq.size()) {
+        const int64_t F = (int64_t)fail2.size();
+        int64_t k = 1;
+        if constexpr (Spec)
+            if (c.steps_per_decode >= 2) k = spec_steps(F, (int64_t)(seq.size() - s), c.steps_per_decode, steps);
+        rows.resize((size_t)(k * F));
+        e2.assign((size_t)(k * F), 0);
+        v2.assign((size_t)(k * F), 0);
+        for (int64_t q = 0; q < k * F; q++) rows[(size_t)q] = fail2[(size_t)(q % F)] - 1;
+        if (k == 1) {
+            rescale_table(eps, seq[s], table);
+            if ((rc = be.decode(rows.data(), F, table, max_iter))) return rc;
+        } else if constexpr (Spec) {
+            packed_table(eps, seq.data() + s, k, c.code_absmax, table);
+            if ((rc = be.decode_spec(rows.data(), F, k, c.code_absmax, table, max_iter))) return rc;
+        }
+        if ((rc = be.stats(rows.data(), k * F, e2.data(), v2.data(), nullptr))) return rc;
+        c.second_decodes++;
+        c.second_rows += k * F;
+        keep.clear();
+        cur.resize((size_t)F);
+        for (int64_t f = 0; f < F; f++) cur[(size_t)f] = (int32_t)f;
+        for (int64_t j = 0; j < k && !cur.empty(); j++) {
+            iter_sec++;
+            next.clear();
+            for (const int32_t f : cur) {
+                const int64_t q = j * F + f;
+                const int32_t v = genie ? e2[(size_t)q] : (v2[(size_t)q] ? 0 : -1);
+                second[(size_t)rows[(size_t)f]] = v;
+                if (faithful) next.clear();  // decoder.py:659-661 resets the list per codeword
+                if (v != 0) next.push_back(f);
+                else keep.push_back((int32_t)q);  // (f leaves the list here: at most one keep per row)
+                c.second_rows_used++;
+            }
+            cur.swap(next);
+        }
+        s += (size_t)k;
         if (!keep.empty() && (rc = be.keep(rows.data(), keep.data(), (int64_t)keep.size()))) return rc;
+        next.clear();
+        for (const int32_t f : cur) next.push_back(fail2[(size_t)f]);
         fail2.swap(next);
     }
     out->t_second_s = seconds_since(t0);
+    if (cnt) *cnt = c;
 
     out->n = n_cw;
     out->first_success = n_cw - (int32_t)fail.size();
@@ -154,6 +235,31 @@ int run(Backend& be, int32_t n_cw, int32_t N, double eps, int32_t max_iter, bool
     if (out->first_errors) std::copy(errors.begin(), errors.end(), out->first_errors);
     if (out->second_errors) std::copy(second.begin(), second.end(), out->second_errors);
     return LDPC_OK;
+}
+
+// One eps2 step per decoder call.
+template <class Backend>
+int run(Backend& be, int32_t n_cw, int32_t N, double eps, int32_t max_iter, bool faithful, ldpc_trial_result* out)
+{
+    return run_impl<false>(be, n_cw, N, eps, max_iter, faithful, 0, out, nullptr);
+}
+
+// run with up to `steps` eps2 steps per decoder call (0 or 1: off, the calls
+// are run's; -1: as many as fit; the caller has refused anything below -1),
+// and the counters.  Every field of *out is run's.  Besides run's operations
+// the backend supplies
+//   int absmax(const int32_t* rows, int64_t F, int32_t* K)
+//       *K = the largest |code| over rows rows[0..F), as int32 (-128 gives 128)
+//   int decode_spec(const int32_t* rows, int64_t F, int64_t k, int32_t K, const double* table, int32_t max_iter)
+//       decode k * F batch rows: row j * F + f is row rows[f] with
+//       K + j * (2K + 1) - 128 added to every code, under the packed table.
+//       rows holds k * F entries, rows[j * F + f] = rows[f], what the stats
+//       and keep calls that follow are handed too.
+template <class Backend>
+int run_spec(Backend& be, int32_t n_cw, int32_t N, double eps, int32_t max_iter, bool faithful, int32_t steps,
+             ldpc_trial_result* out, ldpc_trial_counters* cnt)
+{
+    return run_impl<true>(be, n_cw, N, eps, max_iter, faithful, steps, out, cnt);
 }
 
 // The backend over host buffers: codes [n_cw][N], truth [n_cw][N] or null, and
@@ -185,6 +291,33 @@ struct HostBackend {
         for (int64_t k = 0; k < B; k++) std::memcpy(bcodes.data() + (size_t)k * n, codes + (size_t)rows[k] * n, n);
         return fn(user, bcodes.data(), table, B, max_iter, bhard.data(), bvalid.data());
     }
+    int absmax(const int32_t* rows, int64_t F, int32_t* K)
+    {
+        int32_t m = 0;
+        for (int64_t f = 0; f < F; f++) {
+            const int8_t* r = codes + (size_t)rows[f] * (size_t)N;
+            for (int32_t c = 0; c < N; c++) m = std::max<int32_t>(m, r[c] < 0 ? -(int32_t)r[c] : (int32_t)r[c]);
+        }
+        *K = m;
+        return LDPC_OK;
+    }
+    int decode_spec(const int32_t* rows, int64_t F, int64_t k, int32_t K, const double* table, int32_t max_iter)
+    {
+        const size_t n = (size_t)N, B = (size_t)(k * F);
+        batch = true;
+        bcodes.resize(B * n);
+        bhard.assign(B * n, 0);
+        bvalid.assign(B, 0);
+        for (int64_t j = 0; j < k; j++) {
+            const int32_t shift = K + (int32_t)j * (2 * K + 1) - 128;
+            for (int64_t f = 0; f < F; f++) {
+                const int8_t* src = codes + (size_t)rows[f] * n;
+                int8_t* dst = bcodes.data() + (size_t)(j * F + f) * n;
+                for (size_t c = 0; c < n; c++) dst[c] = (int8_t)((int32_t)src[c] + shift);
+            }
+        }
+        return fn(user, bcodes.data(), table, (int64_t)B, max_iter, bhard.data(), bvalid.data());
+    }
     int stats(const int32_t* rows, int64_t B, int32_t* errors, uint8_t* v, int32_t* re_decode)
     {
         const size_t n = (size_t)N;
@@ -213,25 +346,35 @@ struct HostBackend {
     }
 };
 
-// ldpc_dna_trial_host without the error string: *err gets the message of an
-// argument error.  iters of *out is not touched (the callback reports none).
-inline int run_host(const int8_t* codes, int32_t n_cw, int32_t N, const uint8_t* truth, ldpc_trial_decode_fn fn,
-                    void* user, double eps, int32_t max_iter, int32_t faithful, ldpc_trial_result* out,
-                    std::string* err)
+// ldpc_dna_trial_host_spec without the error string: *err gets the message of
+// an argument error.  iters of *out is not touched (the callback reports
+// none); counters may be null.
+inline int run_host_spec(const int8_t* codes, int32_t n_cw, int32_t N, const uint8_t* truth, ldpc_trial_decode_fn fn,
+                         void* user, double eps, int32_t max_iter, int32_t faithful, int32_t steps,
+                         ldpc_trial_counters* counters, ldpc_trial_result* out, std::string* err)
 {
     *err = check_args(n_cw, N, eps, max_iter, out);
     if (err->empty() && (!codes || !fn)) *err = "null codes or decoder";
+    if (err->empty() && steps < -1) *err = "steps must be >= -1";
     if (!err->empty()) return LDPC_ERR_ARG;
     HostBackend be(codes, truth, n_cw, N, fn, user);
     out->codes_exact = 1;
     out->t_llr_s = 0.0;
-    if (int rc = run(be, n_cw, N, eps, max_iter, faithful != 0, out)) {
+    if (int rc = run_spec(be, n_cw, N, eps, max_iter, faithful != 0, steps, out, counters)) {
         *err = "the decoder callback failed";
         return rc;
     }
     if (out->hard) std::memcpy(out->hard, be.hard.data(), be.hard.size());
     if (out->valid) std::memcpy(out->valid, be.valid.data(), be.valid.size());
     return LDPC_OK;
+}
+
+// ldpc_dna_trial_host: one eps2 step per decode.
+inline int run_host(const int8_t* codes, int32_t n_cw, int32_t N, const uint8_t* truth, ldpc_trial_decode_fn fn,
+                    void* user, double eps, int32_t max_iter, int32_t faithful, ldpc_trial_result* out,
+                    std::string* err)
+{
+    return run_host_spec(codes, n_cw, N, truth, fn, user, eps, max_iter, faithful, 0, nullptr, out, err);
 }
 
 }  // namespace trial

@@ -18,6 +18,9 @@
 //                    re_decode per column, integer atomics only
 //   k_trial_gather   rows of the code matrix -> the contiguous batch of a second decode
 //   k_trial_scatter  rows of a second decode's hard bits -> their rows of hard
+// and, for speculated second decodes (ldpc_trial_set_speculation),
+//   k_trial_absmax       the largest |code| of the failed rows
+//   k_trial_gather_spec  a failed row -> its k shifted copies in the batch, read once
 #pragma once
 
 namespace ldpc {
@@ -164,6 +167,97 @@ __global__ void __launch_bounds__(kCopyThreads) k_trial_scatter(const uint8_t* _
     copy_row_piece(batch + (size_t)k * N, dst + (size_t)i * N, N, vec != 0);
 }
 
+// The 16 code bytes of a thread of the copy grid, from byte o of a row: one
+// uint4 when `vec`, else the bytes below N one by one (others 0).
+__device__ __forceinline__ void load16(const uint8_t* __restrict__ row, int64_t o, int32_t N, bool vec, uint32_t w[4])
+{
+    if (vec) {
+        const uint4 v = *reinterpret_cast<const uint4*>(row + o);
+        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+        return;
+    }
+    for (int d = 0; d < 4; d++) w[d] = 0;
+#pragma unroll
+    for (int c = 0; c < kCopyBytes; c++)
+        if (o + c < N) w[c >> 2] |= (uint32_t)row[o + c] << (8 * (c & 3));
+}
+
+// The largest |code| of 16 code bytes, as int32 (-128 gives 128).
+__device__ __forceinline__ int32_t absmax16(const uint32_t w[4])
+{
+    int32_t m = 0;
+#pragma unroll
+    for (int c = 0; c < kCopyBytes; c++) {
+        const int32_t v = (int32_t)(int8_t)(w[c >> 2] >> (8 * (c & 3)));
+        m = max(m, v < 0 ? -v : v);
+    }
+    return m;
+}
+
+// *out = max(*out, the largest |code| of row rows[blockIdx.y]) (rows of codes
+// [n_rows][N]; blockIdx.y < F; *out starts at 0): a wave's maximum by
+// shuffles, one atomic per wave with a non-zero value.
+__global__ void __launch_bounds__(kCopyThreads) k_trial_absmax(const uint8_t* __restrict__ codes,
+                                                               const int32_t* __restrict__ rows, int32_t n_rows,
+                                                               int32_t N, int32_t vec, int32_t* __restrict__ out,
+                                                               int32_t* __restrict__ bad)
+{
+    const int32_t i = rows[blockIdx.y];  // (the same for the whole block)
+    if (i < 0 || i >= n_rows) {
+        if (threadIdx.x == 0) *bad = 1;
+        return;
+    }
+    const int64_t o = ((int64_t)blockIdx.x * kCopyThreads + threadIdx.x) * kCopyBytes;
+    int32_t m = 0;
+    if (o < N) {
+        uint32_t w[4];
+        load16(codes + (size_t)i * N, o, N, vec != 0, w);
+        m = absmax16(w);
+    }
+    for (int d = 32; d > 0; d >>= 1) m = max(m, __shfl_down(m, d, 64));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+
+// The packed batch of a speculated second decode:
+// out[j * F + f] = src[rows[f]] with K + j * (2K + 1) - 128 added to every
+// code, for f = blockIdx.y < F and j < k; out has at least k * F rows.  A
+// thread loads its 16 bytes once and stores them k times.  The add is per
+// byte, on packed dwords without a carry between bytes.  |code| > K cannot
+// occur when K is the rows' maximum; it would pick a wrong slice of the table,
+// so it is checked and reported as *bad = 2.
+__global__ void __launch_bounds__(kCopyThreads) k_trial_gather_spec(const uint8_t* __restrict__ src,
+                                                                    const int32_t* __restrict__ rows, int32_t F,
+                                                                    int32_t k, int32_t K, int32_t n_rows, int32_t N,
+                                                                    int32_t vec, uint8_t* __restrict__ out,
+                                                                    int32_t* __restrict__ bad)
+{
+    const int32_t f = (int32_t)blockIdx.y, i = rows[f];
+    if (i < 0 || i >= n_rows) {
+        if (threadIdx.x == 0) *bad = 1;
+        return;
+    }
+    const int64_t o = ((int64_t)blockIdx.x * kCopyThreads + threadIdx.x) * kCopyBytes;
+    if (o >= N) return;
+    uint32_t w[4];
+    load16(src + (size_t)i * N, o, N, vec != 0, w);
+    if (absmax16(w) > K) *bad = 2;
+    for (int32_t j = 0; j < k; j++) {
+        const uint32_t s = (uint32_t)((K + j * (2 * K + 1) - 128) & 0xff) * 0x01010101u;
+        uint32_t r[4];
+#pragma unroll
+        for (int d = 0; d < 4; d++)  // bytes of w + bytes of s, mod 256 each
+            r[d] = ((w[d] & 0x7f7f7f7fu) + (s & 0x7f7f7f7fu)) ^ ((w[d] ^ s) & 0x80808080u);
+        uint8_t* dst = out + ((size_t)j * F + f) * N + o;
+        if (vec) {
+            *reinterpret_cast<uint4*>(dst) = make_uint4(r[0], r[1], r[2], r[3]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < kCopyBytes; c++)
+                if (o + c < N) dst[c] = (uint8_t)(r[c >> 2] >> (8 * (c & 3)));
+        }
+    }
+}
+
 }  // namespace
 }  // namespace ldpc
 
@@ -180,6 +274,11 @@ struct ldpc_trial {
     ldpc::dev_ptr<int32_t> iters, biters, errors, re_decode, rows, pos;
     ldpc::dev_ptr<int32_t> ctl;  // [0] a failed range check, [1] the code kernel's overflow word
     bool batch = false;          // the last decode went to bhard / bvalid
+    // speculated second decodes (ldpc_trial_set_speculation)
+    int32_t steps = 0;           // 0: off
+    int64_t cap = 0;             // rows of the batch buffers: n_cw, or ceil64(n_cw) once speculation was enabled
+    ldpc::dev_ptr<int32_t> kmax; // k_trial_absmax's word (allocated when speculation is first enabled)
+    ldpc_trial_counters counters{};  // of the last run
     // the sequencing channel (ldpc_trial_set_strands / ldpc_trial_run_sim): the strands, uploaded once, and
     // the reads of the last run, grown on demand and reused
     int32_t strand_nt = 0;       // 0: no strands set
@@ -215,10 +314,44 @@ struct TrialDev {
         LDPC_HIP(hipMemcpyAsync(&bad, t.ctl.get(), sizeof bad, hipMemcpyDeviceToHost, s));
         if (int rc = t.eng.sync()) return rc;
         if (bad) {
-            set_error(std::string("ldpc_trial: a row index failed its range check in ") + what);
+            set_error(std::string(bad == 2 ? "ldpc_trial: a code is larger than the rows' maximum in "
+                                           : "ldpc_trial: a row index failed its range check in ") + what);
             return LDPC_ERR_DEVICE;
         }
         return LDPC_OK;
+    }
+    dim3 copy_grid(int64_t rows) const
+    {
+        return dim3((unsigned)(((int64_t)t.N + kCopyThreads * kCopyBytes - 1) / (kCopyThreads * kCopyBytes)),
+                    (unsigned)rows);
+    }
+    int absmax(const int32_t* rows, int64_t F, int32_t* K)
+    {
+        LDPC_HIP(hipMemcpyAsync(t.rows.get(), rows, sizeof(int32_t) * (size_t)F, hipMemcpyHostToDevice, s));
+        LDPC_HIP(hipMemsetAsync(t.kmax.get(), 0, sizeof(int32_t), s));
+        hipLaunchKernelGGL(k_trial_absmax, copy_grid(F), dim3(kCopyThreads), 0, s,
+                           reinterpret_cast<const uint8_t*>(t.codes.get()), t.rows.get(), t.B, t.N, (int32_t)vec16(),
+                           t.kmax.get(), t.ctl.get());
+        LDPC_HIP(hipGetLastError());
+        LDPC_HIP(hipMemcpyAsync(K, t.kmax.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        return check_flag("k_trial_absmax");
+    }
+    int decode_spec(const int32_t* rows, int64_t F, int64_t k, int32_t K, const double* table, int32_t max_iter)
+    {
+        const int64_t B = k * F;
+        if (B > t.cap) {  // (k * F <= lanes64(F) <= ceil64(n_cw) by the rule)
+            set_error("ldpc_trial: a speculated batch exceeds the handle's batch buffers");
+            return LDPC_ERR_ARG;
+        }
+        t.batch = true;
+        t.F = (int32_t)B;
+        LDPC_HIP(hipMemcpyAsync(t.rows.get(), rows, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_trial_gather_spec, copy_grid(F), dim3(kCopyThreads), 0, s,
+                           reinterpret_cast<const uint8_t*>(t.codes.get()), t.rows.get(), (int32_t)F, (int32_t)k, K,
+                           t.B, t.N, (int32_t)vec16(), reinterpret_cast<uint8_t*>(t.bcodes.get()), t.ctl.get());
+        LDPC_HIP(hipGetLastError());
+        return t.eng.decode_codes(t.bcodes.get(), table, LDPC_IN_LLR, B, max_iter, t.bhard.get(), nullptr,
+                                  LDPC_POST_LLR, t.biters.get(), t.bvalid.get());
     }
     int decode(const int32_t* rows, int64_t B, const double* table, int32_t max_iter)
     {
@@ -254,7 +387,7 @@ struct TrialDev {
         if (re_decode)
             LDPC_HIP(hipMemcpyAsync(re_decode, t.re_decode.get(), sizeof(int32_t) * (size_t)t.N,
                                     hipMemcpyDeviceToHost, s));
-        return check_flag("k_trial_stats / k_trial_gather");
+        return check_flag("k_trial_stats / k_trial_gather");  // (or k_trial_gather_spec)
     }
     int keep(const int32_t* rows, const int32_t* pos, int64_t n)
     {
@@ -293,6 +426,7 @@ int trial_create(const ldpc_graph* g, int32_t device, int32_t algo, int32_t n_cw
     t->n_cw = n_cw;
     t->N = (int32_t)N;
     t->genie = codewords != nullptr;
+    t->cap = n_cw;
     int rc;
     if ((rc = select_device("ldpc_trial_create", device))) return rc;
     const int64_t pool = n_cw <= kTrialPoolMax ? ((int64_t)n_cw + 63) / 64 * 64 : 0;
@@ -314,13 +448,49 @@ int trial_create(const ldpc_graph* g, int32_t device, int32_t algo, int32_t n_cw
 int trial_run(ldpc_trial& t, int32_t B, double eps, int32_t max_iter, int32_t faithful, ldpc_trial_result* out)
 {
     t.B = B;
+    t.counters = ldpc_trial_counters{};
     TrialDev be(t);
-    if (int rc = trial::run(be, B, t.N, eps, max_iter, faithful != 0, out)) return rc;
+    if (int rc = trial::run_spec(be, B, t.N, eps, max_iter, faithful != 0, t.steps, out, &t.counters)) return rc;
     hipStream_t s = be.s;
     if (out->hard) LDPC_HIP(hipMemcpyAsync(out->hard, t.hard.get(), (size_t)B * (size_t)t.N, hipMemcpyDeviceToHost, s));
     if (out->iters) LDPC_HIP(hipMemcpyAsync(out->iters, t.iters.get(), sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, s));
     if (out->valid) LDPC_HIP(hipMemcpyAsync(out->valid, t.valid.get(), (size_t)B, hipMemcpyDeviceToHost, s));
     return t.eng.sync();
+}
+
+// With steps on for the first time: the batch buffers regrown to ceil64(n_cw)
+// rows (a speculated batch fills the tiles its list occupies) and the word of
+// k_trial_absmax.  The handle changes only when every allocation succeeded.
+int trial_set_speculation(ldpc_trial* t, int32_t steps)
+{
+    if (!t || steps < -1) {
+        set_error("ldpc_trial_set_speculation: null handle, or steps below -1");
+        return LDPC_ERR_ARG;
+    }
+    if (steps != 0 && steps != 1 && !t->kmax) {
+        LDPC_HIP(hipSetDevice(t->device));
+        LDPC_HIP(hipStreamSynchronize(t->eng.stream.get()));
+        const size_t cap = (size_t)trial::lanes64(t->n_cw), mat = cap * (size_t)t->N;
+        dev_ptr<int8_t> bcodes;
+        dev_ptr<uint8_t> bhard, bvalid;
+        dev_ptr<int32_t> biters, errors, rows, pos, kmax;
+        int rc;
+        if ((rc = dev_alloc(bcodes, mat)) || (rc = dev_alloc(bhard, mat)) || (rc = dev_alloc(bvalid, cap)) ||
+            (rc = dev_alloc(biters, cap)) || (rc = dev_alloc(errors, cap)) || (rc = dev_alloc(rows, cap)) ||
+            (rc = dev_alloc(pos, cap)) || (rc = dev_alloc(kmax, 1)))
+            return rc;
+        t->bcodes = std::move(bcodes);
+        t->bhard = std::move(bhard);
+        t->bvalid = std::move(bvalid);
+        t->biters = std::move(biters);
+        t->errors = std::move(errors);
+        t->rows = std::move(rows);
+        t->pos = std::move(pos);
+        t->kmax = std::move(kmax);
+        t->cap = (int64_t)cap;
+    }
+    t->steps = steps;
+    return LDPC_OK;
 }
 
 int trial_run_codes(ldpc_trial* t, const int8_t* codes, int64_t B, double eps, int32_t max_iter, int32_t faithful,
@@ -499,6 +669,19 @@ int ldpc_dna_trial_host(const int8_t* codes, int32_t n_cw, int32_t N, const uint
     });
 }
 
+int ldpc_dna_trial_host_spec(const int8_t* codes, int32_t n_cw, int32_t N, const uint8_t* codewords,
+                             ldpc_trial_decode_fn decode, void* user, double eps, int32_t max_iter, int32_t faithful,
+                             ldpc_trial_result* out, int32_t steps, ldpc_trial_counters* counters)
+{
+    return ldpc::trial_guard("ldpc_dna_trial_host_spec", [&] {
+        std::string err;
+        const int rc = ldpc::trial::run_host_spec(codes, n_cw, N, codewords, decode, user, eps, max_iter, faithful,
+                                                  steps, counters, out, &err);
+        if (rc) set_error("ldpc_dna_trial_host_spec: " + err);
+        return rc;
+    });
+}
+
 ldpc_trial* ldpc_trial_create(const ldpc_graph* g, int32_t device, int32_t algo, int32_t n_cw,
                               const uint8_t* codewords, const ldpc_schedule* schedule, int* err)
 {
@@ -546,6 +729,21 @@ int ldpc_trial_run_codes(ldpc_trial* t, const int8_t* codes, int64_t B, double e
 {
     return ldpc::trial_guard("ldpc_trial_run_codes",
                              [&] { return ldpc::trial_run_codes(t, codes, B, eps, max_iter, faithful, out); });
+}
+
+int ldpc_trial_set_speculation(ldpc_trial* t, int32_t steps)
+{
+    return ldpc::trial_guard("ldpc_trial_set_speculation", [&] { return ldpc::trial_set_speculation(t, steps); });
+}
+
+int ldpc_trial_get_counters(const ldpc_trial* t, ldpc_trial_counters* out)
+{
+    if (!t || !out) {
+        set_error("ldpc_trial_get_counters: null handle or counters");
+        return LDPC_ERR_ARG;
+    }
+    *out = t->counters;
+    return LDPC_OK;
 }
 
 int ldpc_trial_read_codes(ldpc_trial* t, int8_t* codes, int64_t B)

@@ -132,6 +132,16 @@ class TrialResult(C.Structure):
                [(k, C.c_double) for k in ("t_llr_s", "t_first_s", "t_second_s")]
 
 
+class TrialCounters(C.Structure):
+    """ldpc_trial_counters (include/ldpc_amd.h): what the eps2 loop of the last trial handed its decoder."""
+    _fields_ = [(k, C.c_int32) for k in ("second_decodes", "code_absmax", "steps_per_decode", "reserved")] + \
+               [(k, C.c_int64) for k in ("second_rows", "second_rows_used")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k in ("second_decodes", "second_rows", "second_rows_used", "code_absmax",
+                                                   "steps_per_decode")}
+
+
 # ldpc_trial_decode_fn: (user, codes, table, B, max_iter, hard, valid) -> int
 TRIAL_DECODE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int8), C.POINTER(C.c_double), C.c_int64, C.c_int32,
                               C.POINTER(C.c_uint8), C.POINTER(C.c_uint8))
@@ -160,6 +170,11 @@ def _lib():
                                          vp, vp, vp, vp]
         pres = C.POINTER(TrialResult)
         L.ldpc_dna_trial_host.argtypes = [vp, i32, i32, vp, TRIAL_DECODE_FN, vp, C.c_double, i32, i32, pres]
+        pcnt = C.POINTER(TrialCounters)
+        L.ldpc_dna_trial_host_spec.argtypes = [vp, i32, i32, vp, TRIAL_DECODE_FN, vp, C.c_double, i32, i32, pres, i32,
+                                               pcnt]
+        L.ldpc_trial_set_speculation.argtypes = [vp, i32]
+        L.ldpc_trial_get_counters.argtypes = [vp, pcnt]
         L.ldpc_trial_create.argtypes = [vp, i32, i32, i32, vp, C.POINTER(ldpc_amd.Schedule), C.POINTER(C.c_int)]
         L.ldpc_trial_create.restype = vp
         L.ldpc_trial_free.argtypes = [vp]

@@ -236,14 +236,21 @@ class _TrialOut:
 
 
 def decode_trial_host(codes: np.ndarray, codewords: Optional[np.ndarray], decode_cb, eps: float = 0.02,
-                      max_iter: int = 200, faithful: bool = True) -> Dict:
+                      max_iter: int = 200, faithful: bool = True, speculate: int = 0) -> Dict:
     """decode_trial in the library on host buffers (ldpc_dna_trial_host,
     csrc/dna_trial.hpp): codes int8 [n_cw][N] are the whole input, every decode
     goes to decode_cb(codes [B][N], table [256], max_iter) -> (hard [B][N],
     valid [B]), the decode of table[codes + 128].  codewords None: genie-less
     (a row fails iff its valid flag is 0; its error count reads -1).  The
     result has decode_trial's keys (plus valid; iters is not reported by a
-    callback and reads 0)."""
+    callback and reads 0), and the counters second_decodes, second_rows,
+    second_rows_used, code_absmax, steps_per_decode.  speculate (DESIGN.md
+    sec. 8.10; ldpc_dna_trial_host_spec): 0 or 1 one eps2 step per callback,
+    n >= 2 at most n, -1 as many as fit -- the callback then sees the failed
+    rows once per step, their codes shifted into that step's slice of the
+    packed table; the result is the same in every other key."""
+    import ctypes as C
+
     import dna_llr
     mod, L = dna_llr._lib()
     k = np.ascontiguousarray(codes)
@@ -270,13 +277,16 @@ def decode_trial_host(codes: np.ndarray, codewords: Optional[np.ndarray], decode
             return mod.LDPC_ERR_ARG
 
     out = _TrialOut(n_cw, N)
-    rc = L.ldpc_dna_trial_host(dna_llr._p(k), n_cw, N, None if cw is None else dna_llr._p(cw),
-                               dna_llr.TRIAL_DECODE_FN(cb), None, float(eps), int(max_iter), int(bool(faithful)),
-                               out.ref())
+    cnt = dna_llr.TrialCounters()
+    rc = L.ldpc_dna_trial_host_spec(dna_llr._p(k), n_cw, N, None if cw is None else dna_llr._p(cw),
+                                    dna_llr.TRIAL_DECODE_FN(cb), None, float(eps), int(max_iter),
+                                    int(bool(faithful)), out.ref(), int(speculate), C.byref(cnt))
     if raised:
         raise raised[0]
     mod._check(rc)
-    return out.result()
+    res = out.result()
+    res.update(cnt.as_dict())
+    return res
 
 
 class ResidentTrial:
@@ -292,10 +302,16 @@ class ResidentTrial:
         print(report(res))
 
     The times in the result (t_llr_s, t_first_s, t_second_s) are the library's
-    own, returned in ldpc_trial_result."""
+    own, returned in ldpc_trial_result.
+
+    speculate (set_speculation): 0 or 1 one eps2 step per
+    second decode, n >= 2 at most n, -1 as many as fit in the tiles the failed
+    rows occupy anyway.  Every run of the handle uses the setting; the result
+    differs only in the counters second_decodes, second_rows, second_rows_used,
+    code_absmax and steps_per_decode, which every resident result carries."""
 
     def __init__(self, graph, codewords: Optional[np.ndarray] = None, algo="bp", device: int = 0,
-                 n_cw: Optional[int] = None, schedule=None):
+                 n_cw: Optional[int] = None, schedule=None, speculate: int = 0):
         import ctypes as C
 
         import dna_llr
@@ -320,6 +336,23 @@ class ResidentTrial:
                                             None if sch is None else C.byref(sch), C.byref(err))
         if not self._h:
             raise ldpc_amd.LdpcError(err.value, (self._L.ldpc_last_error() or b"").decode(errors="replace"))
+        self.speculate = 0
+        if speculate:
+            self.set_speculation(speculate)
+
+    def set_speculation(self, n: int) -> None:
+        """eps2 steps per second decode for every later run (ldpc_trial_set_speculation)."""
+        self._mod._check(self._L.ldpc_trial_set_speculation(self._h, int(n)))
+        self.speculate = int(n)
+
+    def counters(self) -> Dict:
+        """The counters of the last run (ldpc_trial_get_counters); zeros before the first."""
+        import ctypes as C
+
+        import dna_llr
+        cnt = dna_llr.TrialCounters()
+        self._mod._check(self._L.ldpc_trial_get_counters(self._h, C.byref(cnt)))
+        return cnt.as_dict()
 
     def run_codes(self, codes: np.ndarray, eps: float = 0.02, max_iter: int = 200, faithful: bool = True) -> Dict:
         """The trial of int8 codes [B][N], B <= n_cw, against the first B
@@ -331,7 +364,9 @@ class ResidentTrial:
         out = _TrialOut(max(len(k), 1), self.N)
         self._mod._check(self._L.ldpc_trial_run_codes(self._h, dna_llr._p(k), len(k), float(eps), int(max_iter),
                                                       int(bool(faithful)), out.ref()))
-        return out.result()
+        res = out.result()
+        res.update(self.counters())
+        return res
 
     def _run_reads(self, index_vals, seqs, quals, eps, max_iter, align_fn, faithful, workspace_bytes):
         """ldpc_trial_run_reads -> the result dict, or None when the codes cannot carry the input."""
@@ -348,11 +383,11 @@ class ResidentTrial:
         dna_llr._native_check(mod, rc)
         return self._resident_result(out)
 
-    @staticmethod
-    def _resident_result(out: "_TrialOut") -> Dict:
+    def _resident_result(self, out: "_TrialOut") -> Dict:
         """The result dict of a reads-to-result call that stayed on the device."""
         import dna_llr
         res = out.result()
+        res.update(self.counters())
         kind, stats = out.a["kind"], out.a["stats"]
         res.update(t_llr_s=out.r.t_llr_s, n_erased_strands=int((kind == dna_llr.KIND_NONE).sum()),
                    n_reads_valid=int(stats[0]), n_align_pairs=int(stats[3]), t_align_s=0.0, llr=None, resident=True,

@@ -145,6 +145,7 @@ EXPORTS = [
     "ldpc_trial_read_codes",
     "ldpc_dna_sim_stride", "ldpc_dna_sim_reads_host", "ldpc_dna_sim_reads", "ldpc_trial_set_strands",
     "ldpc_trial_run_sim",
+    "ldpc_dna_trial_host_spec", "ldpc_trial_set_speculation", "ldpc_trial_get_counters",
 ]
 
 

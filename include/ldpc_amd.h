@@ -626,6 +626,46 @@ int ldpc_dna_trial_host(const int8_t *codes, int32_t n_cw, int32_t N, const uint
                         ldpc_trial_decode_fn decode, void *user, double eps, int32_t max_iter, int32_t faithful,
                         ldpc_trial_result *out);
 
+/* Speculated second decodes.  The engine maps one wave
+ * to one (row, tile of 64 lanes), so a second decode of F rows costs what
+ * 64 * ceil(F / 64) rows cost, and the decode of (row, eps2 step) depends on
+ * nothing else.  With speculation on, one decoder call holds the failed rows
+ * under several consecutive eps2 steps and the control flow is replayed over
+ * its results; every field of ldpc_trial_result is what it is without.
+ *
+ *   steps   0 or 1: off, the decoder calls are exactly those above; n >= 2: at
+ *           most n eps2 steps per call; -1: as many as fit; below -1 LDPC_ERR_ARG
+ *   K       the largest |code| over the rows of fail_first (-128 counts 128);
+ *           W = 2K + 1, P = 256 / W: P steps' tables fit side by side in the one
+ *           256-entry table
+ *   a call  for a list of F rows with rem steps left holds
+ *           k = max(1, min(rem, P, 64 * ceil(F / 64) / F, steps if >= 2)) steps:
+ *           only the tiles the batch occupies anyway are filled.  k = 1 is the
+ *           plain decode.  For k >= 2 batch row j * F + f is list row f with
+ *           K + j * W - 128 added to every code, and table[j * W + (c + K)] is
+ *           step j's table entry of code c (0.0 in unused entries): the same
+ *           doubles reach the decoder.
+ *   replay  steps j = 0 .. k - 1 in order, each over the rows still failing,
+ *           as the loop above; results past a row's last step are dropped
+ *
+ * ldpc_trial_counters: of the last run.  With speculation off second_decodes
+ * == second_iterations, second_rows == second_rows_used, and K is not
+ * computed: code_absmax and steps_per_decode read 0. */
+typedef struct ldpc_trial_counters {
+    int32_t second_decodes;   /* decoder calls of the eps2 loop */
+    int32_t code_absmax;      /* K; 0 when the first decode left no failure */
+    int32_t steps_per_decode; /* P */
+    int32_t reserved;
+    int64_t second_rows;      /* rows handed to those calls */
+    int64_t second_rows_used; /* rows whose result the replay consumed */
+} ldpc_trial_counters;
+
+/* ldpc_dna_trial_host with `steps` as above; the callback sees k * F rows and
+ * the packed table.  counters may be NULL. */
+int ldpc_dna_trial_host_spec(const int8_t *codes, int32_t n_cw, int32_t N, const uint8_t *codewords,
+                             ldpc_trial_decode_fn decode, void *user, double eps, int32_t max_iter,
+                             int32_t faithful, ldpc_trial_result *out, int32_t steps, ldpc_trial_counters *counters);
+
 /* The trial handle: one engine (algo LDPC_ALGO_BP or LDPC_ALGO_MSA, its lane
  * pool sized as ldpc_decode_codes sizes it for n_cw codewords), the true
  * codewords [n_cw][N] on `device` (NULL: genie-less), the device code matrix
@@ -659,6 +699,16 @@ int ldpc_trial_run_codes(ldpc_trial *t, const int8_t *codes, int64_t B, double e
 /* The handle's code matrix after a run, rows [0, B) to host codes [B][N]
  * (tests: the code kernel against ldpc_dna_reads_llr's codes). */
 int ldpc_trial_read_codes(ldpc_trial *t, int8_t *codes, int64_t B);
+
+/* Speculated second decodes for every later run of the handle (`steps` as
+ * for ldpc_dna_trial_host_spec; a new handle has 0).  A speculated batch holds
+ * up to 64 * ceil(n_cw / 64) rows: the first call with steps on grows the
+ * handle's batch buffers to that many.  The copies are made on the device
+ * (one kernel reads a failed row once and writes its k shifted copies). */
+int ldpc_trial_set_speculation(ldpc_trial *t, int32_t steps);
+
+/* The counters of the handle's last run (zeros before the first). */
+int ldpc_trial_get_counters(const ldpc_trial *t, ldpc_trial_counters *out);
 
 /* --- the sequencing channel: strands to raw reads -----
  *

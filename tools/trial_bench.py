@@ -2,7 +2,7 @@
 """Whole-trial timing, raw reads to decode result: one JSON line, also written
 to --out.
 
-    python tools/trial_bench.py [--reads R] [--device D] [--out FILE]
+    python tools/trial_bench.py [--reads R] [--device D] [--speculate N] [--out FILE]
 
 The input is one trial's raw reads: --reads simulated raw reads of the DNA
 code (synth.dna_raw_reads, seed 41, 1 % substitutions, deletions 5e-4 per
@@ -22,8 +22,12 @@ Every figure is wall clock around a synchronous call: --warmup untimed calls,
 then --reps timed ones; median, min and max.  The stage times each path
 reports itself (t_llr_s, t_first_s, t_second_s; the resident path's are the
 library's own) are given as medians over the same calls.  Before anything is
-timed the two results are compared in every field.  Needs a GPU; there is no
-fallback.
+timed the two results are compared in every field.  --speculate N (DESIGN.md
+sec. 8.10) times the resident path with up to N eps2 steps per second decode
+(-1: as many as fit; 0, the default: off): the counters of the eps2 loop are
+reported, and before anything is timed the resident result is also compared in
+every field, hard, iters and valid included, with that of the same handle at
+--speculate 0.  Needs a GPU; there is no fallback.
 """
 import argparse
 import json
@@ -45,6 +49,7 @@ FIELDS = ("n", "first_success", "second_success", "fail_first", "fail_second", "
           "second_errors", "erasure_index", "n_erased_strands", "n_reads_valid", "n_align_pairs", "n_reads_dropped",
           "cnumerr_hist")
 STAGES = ("t_llr_s", "t_first_s", "t_second_s")
+COUNTERS = ("second_decodes", "second_rows", "second_rows_used", "code_absmax", "steps_per_decode")
 
 
 def main():
@@ -53,6 +58,7 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--speculate", type=int, default=0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11", "trial_bench.json"))
     a = ap.parse_args()
     if L.device_count() <= a.device:
@@ -73,8 +79,13 @@ def main():
     def resident_path():
         return T.run_raw(raw, eps=0.02)
 
+    plain = resident_path()  # a new handle speculates nothing
+    T.set_speculation(a.speculate)
     old, new = host_path(), resident_path()
-    verified = bool(all(new[k] == old[k] for k in FIELDS) and np.array_equal(new["hard"], old["hard"])
+    same_as_plain = bool(all(new[k] == plain[k] for k in FIELDS)
+                         and all(np.array_equal(new[k], plain[k]) for k in ("hard", "iters", "valid", "kind")))
+    del plain  # (as the parent of this option ran: two results alive while timing)
+    verified = bool(same_as_plain and all(new[k] == old[k] for k in FIELDS) and np.array_equal(new["hard"], old["hard"])
                     and np.array_equal(new["kind"], old["llr"].kind) and new["resident"]
                     and P.report(new) == P.report(old))
 
@@ -95,7 +106,9 @@ def main():
     out = {"tool": "trial_bench", "reads": len(seqs), "read_bytes": int(raw[0][2].sum()), "warmup": a.warmup,
            "reps": a.reps, "first_success": new["first_success"], "second_success": new["second_success"],
            "second_iterations": new["second_iterations"], "erased_strands": new["n_erased_strands"],
-           "erasure_index": len(new["erasure_index"]), "resident_create_ms": round(create_ms, 3)}
+           "erasure_index": len(new["erasure_index"]), "resident_create_ms": round(create_ms, 3),
+           "speculate": a.speculate, "same_as_speculate_0": same_as_plain}
+    out.update({k: new[k] for k in COUNTERS})
     for name, fn in (("host", host_path), ("resident", resident_path)):
         out.update({f"{name}_{k}": v for k, v in measure(fn).items()})
     out["resident_speedup_vs_host"] = round(out["host_ms_median"] / out["resident_ms_median"], 2)
