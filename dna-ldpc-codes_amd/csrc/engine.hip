@@ -398,7 +398,7 @@ int32_t Engine::flags() const
     return (p.nt_d ? LDPC_SCHED_NONTEMPORAL : 0) | (p.cont ? LDPC_SCHED_CONTINUOUS : 0) |
            (p.msa_c ? LDPC_SCHED_MSA_COMPRESSED : 0) | (p.res ? LDPC_SCHED_RESIDENT : 0) |
            (p.syn_blocks > 0 ? LDPC_SCHED_SPLIT_SYNDROME : 0) | (p.first_fp ? LDPC_SCHED_FIRST_FROM_PRIOR : 0) |
-           (p.handover ? LDPC_SCHED_HANDOVER : 0) |
+           (p.handover ? LDPC_SCHED_HANDOVER : 0) | (p.fuse_block >= 0 ? LDPC_SCHED_FUSE_ROW_BLOCK : 0) |
            (sched.flags & (LDPC_SCHED_LR_TABLE | LDPC_SCHED_DEBUG_NO_DRAIN | LDPC_SCHED_DEBUG_BAD_LANE));
 }
 
@@ -495,6 +495,12 @@ int Engine::launch_check(double* scratch, int64_t t0, unsigned gt, const dev::Re
     if (rstep) {
         if (!p.res || p.msa_c || scratch != v2c.get()) { set_error("resident check: bad state"); return LDPC_ERR_ARG; }
         if (msa) return launch(kc, (k_check_msa<72, false, true>), grid, blk, v2c, v2c, active, M, E, t0, *rstep);
+        if (p.fuse_block >= 0) {  // the fused row block's messages belong to k_var_bp_fused (launch_var)
+            if (t0 != 0) { set_error("resident check: bad state"); return LDPC_ERR_ARG; }
+            const int32_t Q = M / 8;
+            return launch(kc, (k_check_bp_skip<72>), grid, blk, v2c, v2c, M, E, p.fuse_block * Q, (p.fuse_block + 1) * Q,
+                          *rstep);
+        }
         return launch(kc, (k_check_bp<72, false, true>), grid, blk, v2c, v2c, active, M, E, t0, *rstep);
     }
     if (p.msa_c) {  // 1-D XCD-affine grid (k_check_msa_c)
@@ -557,6 +563,16 @@ int Engine::launch_var(double* scratch, int64_t t0, unsigned gt, double* pt, con
                 rc = launch(kc, (k_var_msa_c<72, 8, CONT(), CPW(), NT(), PC()>), dim3(nb), dim3(256), rec, meta, v2c, prior,
                             hard, d_sgn, active, dg.col_er, pt, N, M, E, t0, (uint32_t)gt, dg.msa_pa, dg.msa_pb, rf);
         }, cnt, p.nt_d, pc);
+    } else if (reg8 && p.fuse_block >= 0 && cnt && inplace) {
+        // the resident pool's steps with a fused row block (plan_engine: BP,
+        // (8, 72)-regular, default columns per wave): one workgroup per row of
+        // the block, which also finishes that row's check (k_check_bp_skip)
+        if (t0 != 0 || timing) { set_error("fused row block: bad state"); return LDPC_ERR_ARG; }
+        const dim3 grid((unsigned)(M / 8), gt);
+        with_bools([&](auto PC) {
+            rc = launch(kc, (k_var_bp_fused<kFuseWaves, kFuseCpw, PC()>), grid, dim3(64 * kFuseWaves), v2c, prior, hard,
+                        active, dg.col_edge, dg.col_idx, pt, N, E, p.fuse_block * (M / 8), rf);
+        }, pc);
     } else if (reg8) {
         const int want = var_cpw_for(rf);
         const int cpw = (want != 3 && N % (4 * want) == 0) ? want : 1;

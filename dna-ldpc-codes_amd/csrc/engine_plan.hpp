@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <utility>
+#include <vector>
 
 #include "../../include/ldpc_amd.h"
 #include "graph.hpp"
@@ -36,7 +37,12 @@ constexpr int32_t kAllFlags = kDefaultFlags | LDPC_SCHED_DEBUG_NO_DRAIN | LDPC_S
 // whether the caller chose the resident pool (the auto-disable rule for
 // large explicit pools applies only when it did not).  A caller's bits
 // outside kAllFlags are dropped, so no caller can mark a schedule resolved.
-constexpr int32_t kResolved = 1 << 30, kResChosen = 1 << 29;
+// kNoFuse: the caller turned LDPC_SCHED_FUSE_ROW_BLOCK off.  That flag is on
+// by default, but a resolved schedule carries it as this mark and not in the
+// low word: the resolved words of bits 0..15 are what they were before the
+// flag existed (tests/test_engine_plan.py states them), and the rule above
+// still holds.
+constexpr int32_t kResolved = 1 << 30, kResChosen = 1 << 29, kNoFuse = 1 << 28;
 
 // A caller's ldpc_schedule with every field resolved: flags_set covers all
 // bits, zero fields replaced by the defaults (include/ldpc_amd.h).  Two
@@ -46,10 +52,12 @@ inline ldpc_schedule resolve_schedule(const ldpc_schedule* s)
 {
     ldpc_schedule r{};
     if (s) r = *s;
+    const bool no_fuse = (r.flags_set & LDPC_SCHED_FUSE_ROW_BLOCK) && !(r.flags & LDPC_SCHED_FUSE_ROW_BLOCK);
     r.flags_set &= kAllFlags;
     r.flags = (kDefaultFlags & ~r.flags_set) | (r.flags & r.flags_set);
     r.flags &= kAllFlags;
-    r.flags_set = kAllFlags | kResolved | ((r.flags_set & LDPC_SCHED_RESIDENT) ? kResChosen : 0);
+    r.flags_set = kAllFlags | kResolved | ((r.flags_set & LDPC_SCHED_RESIDENT) ? kResChosen : 0) |
+                  (no_fuse ? kNoFuse : 0);
     if (r.group_tiles == 0) r.group_tiles = -2;  // per-algorithm default, resolved by plan_engine
     // (3: compressed min-sum only; the fp64 variable kernels take 1, 2, 4 or
     // 8); -2: the default, chosen per decode by the prior's form (var_cpw_for)
@@ -111,11 +119,37 @@ inline size_t msa_scratch_bytes(int64_t tiles, int32_t M)
     return (size_t)tiles * M * kTile * (kMsaRecPlanes * sizeof(double) + sizeof(uint16_t));
 }
 
+// The fused row block (LDPC_SCHED_FUSE_ROW_BLOCK) of a graph with dv row
+// blocks of Q = M / dv rows: the first block a whose rows [aQ, (a+1)Q) hold
+// every column exactly once, -1 when there is none.  Each row of that block
+// then owns its dc columns: no other row of the block touches them.
+inline int fuse_row_block_of(const HostGraph& g)
+{
+    const int dv = g.dv_max;
+    if (dv <= 0 || g.M % dv != 0 || !g.regular_dc) return -1;
+    const int32_t Q = g.M / dv;
+    if ((int64_t)Q * g.dc_max != g.N) return -1;
+    std::vector<uint8_t> seen((size_t)g.N);
+    for (int a = 0; a < dv; a++) {
+        std::fill(seen.begin(), seen.end(), (uint8_t)0);
+        bool once = true;
+        for (int64_t e = (int64_t)a * Q * g.dc_max; once && e < (int64_t)(a + 1) * Q * g.dc_max; e++) {
+            uint8_t& c = seen[(size_t)g.col_idx[(size_t)e]];
+            once = c == 0;
+            c = 1;
+        }
+        if (once) return a;  // Q * dc = N distinct columns: all of them
+    }
+    return -1;
+}
+
 struct EnginePlan {
     bool msa_c = false;       // min-sum with compressed c2v (records + meta words, k_check_msa_c / k_var_msa_c)
     bool cont = false;        // continuous batching: refill lanes as codewords finish
     bool res = false;         // resident pool: a few tiles iterated in place, syndrome in the check kernel
     bool handover = false;    // res, (8,72)-regular: a lane is refilled during its codeword's last update (ResStep::last)
+    int fuse_block = -1;      // res, (8,72)-regular BP: the row block whose check runs in the variable kernel
+                              // (k_var_bp_fused; k_check_bp skips its messages), -1: none
     bool nt_d = false;        // nontemporal loads/stores of the v2c ("d") stream
     bool first_fp = false;    // single-fill BP: the first check reads the prior (k_check_bp_first)
     bool debug_no_drain = false;  // LDPC_SCHED_DEBUG_NO_DRAIN: the host ignores a drained pool
@@ -169,6 +203,10 @@ inline EnginePlan plan_engine(const HostGraph& g, int algo, int64_t chunk, const
     // hand-over: k_check_bp / k_check_msa<72, ., RES> + k_var_m in place only
     p.handover = sched_flag(s, LDPC_SCHED_HANDOVER) && p.res && reg_72_8 &&
                  (algo == LDPC_ALGO_BP || algo == LDPC_ALGO_MSA);
+    // fused row block: k_var_bp_fused in place of k_var_m at its default
+    // columns per wave (an explicit var_cpw keeps k_var_m)
+    if (!(s.flags_set & kNoFuse) && p.res && reg_72_8 && algo == LDPC_ALGO_BP && s.var_cpw == -2)
+        p.fuse_block = fuse_row_block_of(g);
     p.debug_no_drain = sched_flag(s, LDPC_SCHED_DEBUG_NO_DRAIN);
     p.debug_bad_lane = sched_flag(s, LDPC_SCHED_DEBUG_BAD_LANE);
     p.var_cpw = s.var_cpw;

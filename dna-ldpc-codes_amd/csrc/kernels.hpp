@@ -506,11 +506,17 @@ __device__ __forceinline__ void check_bp_compute(const double (&x)[DC], typename
 // parity over the previous variable phase's ballots, and every block ends in
 // res_arrive (no early exit).
 // Block rb of nrb row blocks of tile t; lr_t = the tile's c2v messages.
-template <int DC, bool NT, bool RES>
+// SKIP (RES only, the fused row block): the messages of rows [skip_lo,
+// skip_hi) belong to k_var_bp_fused; a wave on such a row takes only the
+// row's parity (and the pending plane's), and ends in res_arrive as every
+// other.
+template <int DC, bool NT, bool RES, bool SKIP = false>
 __device__ __forceinline__ void check_bp_block(typename Msg<RES>::in dmsg, typename Msg<RES>::out lr_t,
                                                const uint64_t* __restrict__ active, int32_t M, int64_t E,
-                                               int64_t t, uint32_t rb, uint32_t nrb, const ResStep& rs)
+                                               int64_t t, uint32_t rb, uint32_t nrb, const ResStep& rs,
+                                               int32_t skip_lo = 0, int32_t skip_hi = 0)
 {
+    static_assert(RES || !SKIP, "rows are skipped in the resident pool only");
     const int lane = lane_id();
     const int32_t row = (int32_t)rb * 4 + wave_id();
     const uint64_t act = RES ? rs.cs.occupied[t] : active[t];
@@ -541,7 +547,9 @@ __device__ __forceinline__ void check_bp_block(typename Msg<RES>::in dmsg, typen
         const int64_t b0 = rs.cs.lane_b[t * TILE + lane];
         const uint64_t pend = pend_lanes(rs, t);
         uint64_t par = 0;
-        if (row < M && act != 0) {
+        if (SKIP && row >= skip_lo && row < skip_hi) {  // wave-uniform
+            if (act != 0) par = row_parity<DC>(rs.hard + (size_t)t * rs.N, rs.col_idx + (size_t)row * DC);
+        } else if (row < M && act != 0) {
             const int32_t* __restrict__ cols = rs.col_idx + (size_t)row * DC;
             const int32_t c0 = cols[lane < DC ? lane : DC - 1];
             const int32_t c1 = cols[TILE + lane < DC ? TILE + lane : DC - 1];
@@ -666,6 +674,16 @@ __global__ __launch_bounds__(256, 2) void k_check_bp(typename Msg<RES>::in dmsg,
                                 gridDim.x, rs);
 }
 
+// The resident pool's check next to k_var_bp_fused: same grid, rows [skip_lo,
+// skip_hi) -- the fused row block, skip_hi <= M -- without their messages.
+template <int DC>
+__global__ __launch_bounds__(256, 2) void k_check_bp_skip(const double* dmsg, double* lr, int32_t M, int64_t E,
+                                                          int32_t skip_lo, int32_t skip_hi, ResStep rs)
+{
+    check_bp_block<DC, false, true, true>(dmsg, lr + (size_t)blockIdx.y * E * TILE, nullptr, M, E, blockIdx.y,
+                                          blockIdx.x, gridDim.x, rs, skip_lo, skip_hi);
+}
+
 // Generic row degree: the prefix products go through the lr array exactly as
 // the reference does (e->lr = dl in the forward pass, dec.cpp:650-653).
 __global__ __launch_bounds__(256) void k_check_bp_gen(const double* __restrict__ dmsg, double* __restrict__ lr,
@@ -703,6 +721,126 @@ __device__ __forceinline__ double prior_at(const double* __restrict__ prior, con
 {
     if constexpr (PC) return rf.ptab[rf.pcode[i] + kCodeBias];
     else return prior[i];
+}
+
+// ---------------------------------------------------------------------------
+// One column of the variable phase in one lane: the arithmetic of the regular
+// variable kernels (var_m_block, and k_var_bp_fused for BP), stated once.
+// The comment of var_m_block gives the recurrences and their reference lines.
+// ---------------------------------------------------------------------------
+// Hand-over: the final update of a last lane (ls) yields only P / L and the
+// decision hf; the posterior of its codeword lb goes out when lok.
+template <bool MSA, int DV>
+__device__ __forceinline__ bool var_column_final(bool ls, double pvc, const double (&l)[DV], bool lok,
+                                                 const Refill& rf, int64_t lb, int32_t N, int32_t j)
+{
+    bool hf = false;
+    if (ls) {
+        double p = pvc;
+        if (MSA) {
+#pragma unroll
+            for (int s = 0; s < DV; ++s) p = p + l[s];
+            hf = !(p > 0);
+            if (lok && rf.post_out) rf.post_out[(size_t)lb * N + j] = p;
+        } else {
+#pragma unroll
+            for (int s = 0; s < DV; ++s) p = p * l[s];
+            if (__builtin_isnan(p)) p = 1.0;
+            hf = (p <= 1.0);
+            if (lok && rf.post_out) rf.post_out[(size_t)lb * N + j] = rf.post_ratio ? p : log(p);
+        }
+    }
+    return hf;
+}
+
+// A finished codeword's posterior of its exit (fn iterations), to post_out[ob].
+template <bool MSA, bool PC>
+__device__ __forceinline__ void var_column_fin_post(const Refill& rf, const double* __restrict__ prior,
+                                                    const double* post, size_t pj, size_t ob, int32_t fn)
+{
+    const double pv = fn > 0 ? post[pj] : prior_at<PC>(prior, rf, pj);
+    if (MSA) rf.post_out[ob] = pv;
+    else {
+        const double P = __builtin_isnan(pv) ? 1.0 : pv;
+        rf.post_out[ob] = rf.post_ratio ? P : log(P);
+    }
+}
+
+// The lane's outgoing messages dv, the prior np it holds after the step and
+// its decision h: Init from the input value x for a refilled lane (fr), the
+// update from the prior pvc and the incoming messages l for a live lane that
+// is not in its final update (ls), zeros for every other lane.
+template <bool MSA, int DV, bool PC>
+__device__ __forceinline__ void var_column(bool live, bool fr, bool ls, double pvc, double x, const double (&l)[DV],
+                                           const Refill& rf, double* post, size_t pj, double (&dv)[DV], double& np,
+                                           bool& h)
+{
+    h = false;
+#pragma unroll
+    for (int s = 0; s < DV; ++s) dv[s] = 0.0;
+    np = 0.0;  // the prior this lane holds after the step (refill: its new one)
+    if (live) np = pvc;
+    if (fr) {  // Init_Belief_Propagation / Init_MSA_INF for a refilled lane
+        if (MSA) {
+            np = x;
+#pragma unroll
+            for (int s = 0; s < DV; ++s) dv[s] = x;
+            h = !(x > 0);
+        } else {
+            // PC: the table holds LR already (the host exp of the caller's LLR table)
+            const double LR0 = (!PC && rf.in_is_llr) ? exp(x) : x;
+            np = LR0;
+            const double d0 = 1.0 - 2.0 / (1.0 + LR0);
+#pragma unroll
+            for (int s = 0; s < DV; ++s) dv[s] = d0;
+            h = (LR0 < 1.0);
+        }
+    } else if (live && !ls) {
+        if (MSA) {  // v2c_s = LLR + c_0 + ... (skipping c_s); L = LLR + all
+#pragma unroll
+            for (int s = 0; s < DV; ++s) {
+                double sum = pvc;
+#pragma unroll
+                for (int r = 0; r < DV; ++r)
+                    if (r != s) sum = sum + l[r];
+                dv[s] = sum;
+            }
+            double L = pvc;
+#pragma unroll
+            for (int s = 0; s < DV; ++s) L = L + l[s];
+            h = !(L > 0);
+            if (post) post[pj] = L;
+        } else {
+            double pr[DV];
+            double p = pvc;
+#pragma unroll
+            for (int s = 0; s < DV; ++s) { pr[s] = p; p = p * l[s]; }
+            if (__builtin_isnan(p)) p = 1.0;
+            h = (p <= 1.0);
+            if (post) post[pj] = p;
+            double acc = 1.0;
+#pragma unroll
+            for (int s = DV - 1; s >= 0; --s) {
+                double v = pr[s] * acc;
+                if (__builtin_isnan(v)) v = 1.0;
+                acc = acc * l[s];
+                dv[s] = 1.0 - 2.0 / (1.0 + v);
+            }
+        }
+    }
+}
+
+// The ballot of the wave's decisions h for column j, merged by lane 0 into
+// hard[t][j] under the tile's touched lanes (the other lanes' bits stay).
+__device__ __forceinline__ void merge_touched(uint64_t* __restrict__ hard, int64_t t, int32_t N, int32_t j,
+                                              uint64_t touched, bool h, int lane)
+{
+    const uint64_t m = __ballot(h);
+    if (lane == 0 && touched) {
+        const size_t o = (size_t)t * N + j;
+        const uint64_t old = (touched == ~0ull) ? 0ull : hard[o];
+        hard[o] = (old & ~touched) | (m & touched);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -810,22 +948,7 @@ __device__ __forceinline__ void var_m_block(typename Msg<INPLACE>::in c2v_t, typ
         uint64_t hwf[CPW];
 #pragma unroll
         for (int c = 0; c < CPW; ++c) {
-            bool hf = false;
-            if (ls) {
-                double p = pv[c];
-                if (MSA) {
-#pragma unroll
-                    for (int s = 0; s < DV; ++s) p = p + l[c][s];
-                    hf = !(p > 0);
-                    if (lok && rf.post_out) rf.post_out[(size_t)lb * N + j0 + c] = p;
-                } else {
-#pragma unroll
-                    for (int s = 0; s < DV; ++s) p = p * l[c][s];
-                    if (__builtin_isnan(p)) p = 1.0;
-                    hf = (p <= 1.0);
-                    if (lok && rf.post_out) rf.post_out[(size_t)lb * N + j0 + c] = rf.post_ratio ? p : log(p);
-                }
-            }
+            const bool hf = var_column_final<MSA, DV>(ls, pv[c], l[c], lok, rf, lb, N, j0 + c);
             hwf[c] = __ballot(hf);
             if (lane == 0) rf.hard_fin[(size_t)t * N + j0 + c] = hwf[c];
         }
@@ -847,70 +970,11 @@ __device__ __forceinline__ void var_m_block(typename Msg<INPLACE>::in c2v_t, typ
     for (int c = 0; c < CPW; ++c) {
         const int32_t j = j0 + c;
         const size_t pj = ((size_t)t * N + j) * TILE + lane;
-        if (CONT && fl && fok && rf.post_out) {  // finished codeword: posterior of its exit
-            const size_t ob = (size_t)fb * N + j;
-            const double pv = fn > 0 ? post[pj] : prior_at<PC>(prior, rf, pj);
-            if (MSA) rf.post_out[ob] = pv;
-            else {
-                const double P = __builtin_isnan(pv) ? 1.0 : pv;
-                rf.post_out[ob] = rf.post_ratio ? P : log(P);
-            }
-        }
-        bool h = false;
-        double dv[DV];
-#pragma unroll
-        for (int s = 0; s < DV; ++s) dv[s] = 0.0;
-        double np = 0.0;  // the prior this lane holds after the step (refill: its new one)
-        if (live) np = pv[c];
-        if (fr) {  // Init_Belief_Propagation / Init_MSA_INF for a refilled lane
-            const double x = xin[c];
-            if (MSA) {
-                np = x;
-#pragma unroll
-                for (int s = 0; s < DV; ++s) dv[s] = x;
-                h = !(x > 0);
-            } else {
-                // PC: the table holds LR already (the host exp of the caller's LLR table)
-                const double LR0 = (!PC && rf.in_is_llr) ? exp(x) : x;
-                np = LR0;
-                const double d0 = 1.0 - 2.0 / (1.0 + LR0);
-#pragma unroll
-                for (int s = 0; s < DV; ++s) dv[s] = d0;
-                h = (LR0 < 1.0);
-            }
-        } else if (live && !ls) {
-            if (MSA) {  // v2c_s = LLR + c_0 + ... (skipping c_s); L = LLR + all
-#pragma unroll
-                for (int s = 0; s < DV; ++s) {
-                    double sum = pv[c];
-#pragma unroll
-                    for (int r = 0; r < DV; ++r)
-                        if (r != s) sum = sum + l[c][r];
-                    dv[s] = sum;
-                }
-                double L = pv[c];
-#pragma unroll
-                for (int s = 0; s < DV; ++s) L = L + l[c][s];
-                h = !(L > 0);
-                if (post) post[pj] = L;
-            } else {
-                double pr[DV];
-                double p = pv[c];
-#pragma unroll
-                for (int s = 0; s < DV; ++s) { pr[s] = p; p = p * l[c][s]; }
-                if (__builtin_isnan(p)) p = 1.0;
-                h = (p <= 1.0);
-                if (post) post[pj] = p;
-                double acc = 1.0;
-#pragma unroll
-                for (int s = DV - 1; s >= 0; --s) {
-                    double v = pr[s] * acc;
-                    if (__builtin_isnan(v)) v = 1.0;
-                    acc = acc * l[c][s];
-                    dv[s] = 1.0 - 2.0 / (1.0 + v);
-                }
-            }
-        }
+        if (CONT && fl && fok && rf.post_out)  // finished codeword: posterior of its exit
+            var_column_fin_post<MSA, PC>(rf, prior, post, pj, (size_t)fb * N + j, fn);
+        bool h;
+        double dv[DV], np;
+        var_column<MSA, DV, PC>(live, fr, ls, pv[c], xin[c], l[c], rf, post, pj, dv, np, h);
         if (CONT && fr) {
             if constexpr (PC) rf.pcode[pj] = kin[c];
             else prior[pj] = np;
@@ -923,12 +987,7 @@ __device__ __forceinline__ void var_m_block(typename Msg<INPLACE>::in c2v_t, typ
 #pragma unroll
             for (int s = 0; s < DV; ++s) st<NT>(v2c + (tb + eid[c][s]) * TILE + lane, dv[s]);
         }
-        const uint64_t m = __ballot(h);
-        if (lane == 0 && touched) {
-            const size_t o = (size_t)t * N + j;
-            const uint64_t old = (touched == ~0ull) ? 0ull : hard[o];
-            hard[o] = (old & ~touched) | (m & touched);
-        }
+        merge_touched(hard, t, N, j, touched, h, lane);
     }
     // the reports of skipped accesses: the lane's pool slot (the indices need
     // not stay live; cont_lanes reports an out-of-range index itself)
@@ -948,6 +1007,182 @@ __global__ __launch_bounds__(256) void k_var_m(typename Msg<INPLACE>::in c2v, ty
     var_m_block<MSA, DV, NT, CONT, CPW, INPLACE, PC>(c2v + (size_t)blockIdx.y * E * TILE, v2c, prior, hard, active,
                                                  col_edge, post, N, E, t0 + blockIdx.y,
                                                  xcd_block(blockIdx.x, gridDim.x), rf);
+}
+
+// ---------------------------------------------------------------------------
+// Resident pool, BP on an (8, 72)-regular code, fused row block
+// (EnginePlan::fuse_block = a: rows [row0, row0 + M / 8) hold every column
+// exactly once).  One workgroup per (row of that block, tile): the row's 72
+// columns belong to this workgroup alone, so it runs their variable phase --
+// W waves x KW = 72 / W columns, CPW at a time, the arithmetic and stores of
+// var_m_block<false, 8, false, true, ., true, PC> (var_column and its
+// companions) -- and keeps the row's own variable->check messages in LDS
+// instead of storing them.  After one barrier it finishes the row's check
+// update from them: check_bp_compute's operations in its order (prefix
+// products from slot 0 up, suffix from slot 71 down, lr = (1 + t) / (1 - t)),
+// each wave for its own KW edges, recomputing the prefix before and the
+// suffix behind them; the results go to the edges in place, where the
+// next variable phase reads them.  k_check_bp_skip leaves those rows'
+// messages alone.  So the block's d never reaches memory: the next check
+// moves 7/8 of its message bytes.
+// In place without hazards across workgroups: every edge of a column is read
+// and written by the workgroup that owns the column, and the row's lr stores
+// follow the barrier, after every lr load of the workgroup.
+// Every condition in front of the barrier is per tile (workgroup-uniform).
+// grid (M / 8, tiles), block 64 * W.
+// W = 8, CPW = 3 (kFuseWaves, kFuseCpw): 24 outstanding 512-B loads per wave
+// and round, 112 VGPRs, 36 KB LDS, no scratch, 4 waves per SIMD.  The fastest
+// of the geometries timed (4 x 2, 4 x 3, 6 x 2, 6 x 3, 8 x 3); their
+// resources and times are in profiles/r14/README.md.
+// ---------------------------------------------------------------------------
+constexpr int kFuseWaves = 8, kFuseCpw = 3;
+template <int W, int CPW, bool PC>
+__global__ __launch_bounds__(64 * W) void k_var_bp_fused(double* msg, double* __restrict__ prior,
+                                                         uint64_t* __restrict__ hard,
+                                                         const uint64_t* __restrict__ active,
+                                                         const int32_t* __restrict__ col_edge,
+                                                         const int32_t* __restrict__ col_idx, double* post, int32_t N,
+                                                         int64_t E, int32_t row0, Refill rf)
+{
+    constexpr int DC = 72, DV = 8, KW = DC / W;
+    static_assert(DC % W == 0 && KW % CPW == 0, "the row's columns split evenly over the waves and their rounds");
+    __shared__ double sd[DC][TILE];  // the row's d, slot k = the column's position in the row
+    const int lane = lane_id(), w = wave_id();
+    const int64_t t = blockIdx.y;
+    const int32_t row = row0 + (int32_t)xcd_block(blockIdx.x, gridDim.x);
+    const uint64_t act = active[t];
+    const uint64_t frm = rf.fresh[t];
+    const uint64_t touched = act | frm;
+    const uint64_t fm = rf.fin ? rf.fin[t] : 0ull;
+    const uint64_t lastm = rf.last ? rf.last[t] : 0ull;
+    if (touched == 0 && fm == 0) return;  // per tile
+    const bool live = (act >> lane) & 1ull;
+    const bool fr = (frm >> lane) & 1ull;
+    const bool fl = (fm >> lane) & 1ull;
+    const bool ls = (lastm >> lane) & 1ull;
+    int64_t fb = 0;
+    int32_t fn = 0;
+    if (fl) {
+        fb = rf.fin_b[t * TILE + lane];
+        fn = rf.fin_n[t * TILE + lane];
+    }
+    double* m_t = msg + (size_t)t * E * TILE;  // the tile's messages (a scalar base: the lane goes into the offset)
+    const int k0 = w * KW;
+    const int32_t e0 = row * DC + k0;  // the wave's first edge of the row
+    bool bad_in = false;
+    int bad_v = 0;  // (a VGPR, as in var_m_block)
+    size_t rb = 0;
+    if (fr) {
+        rb = (size_t)refill_row(rf.lane_b[t * TILE + lane], rf, bad_in) * N;
+        bad_v = bad_in ? 1 : 0;
+    }
+    const int64_t lb = ls ? rf.pend_b[t * TILE + lane] : 0;
+    const bool lok = out_ok(lb, rf), fok = out_ok(fb, rf);
+    const bool keep = line_occupied(touched, lane) || fr || live;  // whole-line stores, as var_m_block
+#pragma unroll
+    for (int r = 0; r < KW; r += CPW) {
+        int32_t j[CPW], eid[CPW][DV];
+#pragma unroll
+        for (int c = 0; c < CPW; ++c) j[c] = col_idx[e0 + r + c];
+#pragma unroll
+        for (int c = 0; c < CPW; ++c)
+#pragma unroll
+            for (int s = 0; s < DV; ++s) eid[c][s] = col_edge[(size_t)j[c] * DV + s];
+        double l[CPW][DV], pv[CPW], xin[CPW];
+        int8_t kin[CPW];
+        if (fr) {
+#pragma unroll
+            for (int c = 0; c < CPW; ++c) {
+                if constexpr (PC) kin[c] = rf.in_code[rb + j[c]];
+                else xin[c] = rf.in[rb + j[c]];
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int c = 0; c < CPW; ++c) {
+                pv[c] = prior_at<PC>(prior, rf, ((size_t)t * N + j[c]) * TILE + lane);
+#pragma unroll
+                for (int s = 0; s < DV; ++s) l[c][s] = m_t[(size_t)eid[c][s] * TILE + lane];
+            }
+        }
+        if constexpr (PC) {
+            if (fr) {
+#pragma unroll
+                for (int c = 0; c < CPW; ++c) xin[c] = rf.ptab[kin[c] + kCodeBias];
+            }
+        }
+        if (lastm != 0) {  // hand-over (var_m_block): final updates, outputs and the second ballot plane
+#pragma unroll
+            for (int c = 0; c < CPW; ++c) {
+                const uint64_t hwf = __ballot(var_column_final<false, DV>(ls, pv[c], l[c], lok, rf, lb, N, j[c]));
+                if (lane == 0) rf.hard_fin[(size_t)t * N + j[c]] = hwf;
+                if (ls && lok) store_fin_hard<1>(rf, &hwf, lb, N, j[c], lane);
+            }
+        }
+        if (fl && fok) {  // finished codeword: hard bits of its exit (ballots before this step's update)
+#pragma unroll
+            for (int c = 0; c < CPW; ++c) {
+                const uint64_t hw = hard[(size_t)t * N + j[c]];
+                store_fin_hard<1>(rf, &hw, fb, N, j[c], lane);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CPW; ++c) {
+            const size_t pj = ((size_t)t * N + j[c]) * TILE + lane;
+            if (fl && fok && rf.post_out) var_column_fin_post<false, PC>(rf, prior, post, pj, (size_t)fb * N + j[c], fn);
+            bool h;
+            double dv[DV], np;
+            var_column<false, DV, PC>(live, fr, ls, pv[c], xin[c], l[c], rf, post, pj, dv, np, h);
+            if (fr) {
+                if constexpr (PC) rf.pcode[pj] = kin[c];
+                else prior[pj] = np;
+            }
+            const int32_t ea = e0 + r + c;  // the column's edge in this row: to LDS (a wave-uniform choice per slot)
+            if (keep) {
+#pragma unroll
+                for (int s = 0; s < DV; ++s) {
+                    if (eid[c][s] == ea) sd[k0 + r + c][lane] = dv[s];
+                    else m_t[(size_t)eid[c][s] * TILE + lane] = dv[s];
+                }
+            }
+            merge_touched(hard, t, N, j[c], touched, h, lane);
+        }
+    }
+    if (lastm != 0 && ls && !lok) lane_fault(rf.fault, kFaultOutput, t * TILE + lane);
+    if (fl && !fok) lane_fault(rf.fault, kFaultOutput, t * TILE + lane);
+    asm volatile("" : "+v"(bad_v));
+    if (bad_v) lane_fault(rf.fault, kFaultRefill, t * TILE + lane);
+    __syncthreads();
+    if (touched == 0) return;  // a tile that only hands out finished codewords: no messages
+    // the row's check update for edges k0 .. k0 + KW - 1 (check_bp_compute's
+    // chains; the other waves' groups of KW slots are multiplied through)
+    double p = 1.0;
+    for (int g = 0; g < w; ++g) {
+        double y[KW];
+#pragma unroll
+        for (int i = 0; i < KW; ++i) y[i] = sd[g * KW + i][lane];
+#pragma unroll
+        for (int i = 0; i < KW; ++i) p = p * y[i];
+    }
+    double x[KW], pk[KW];
+#pragma unroll
+    for (int i = 0; i < KW; ++i) x[i] = sd[k0 + i][lane];
+#pragma unroll
+    for (int i = 0; i < KW; ++i) { pk[i] = p; p = p * x[i]; }
+    double sfx = 1.0;
+    for (int g = W - 1; g > w; --g) {
+        double y[KW];
+#pragma unroll
+        for (int i = 0; i < KW; ++i) y[i] = sd[g * KW + i][lane];
+#pragma unroll
+        for (int i = KW - 1; i >= 0; --i) sfx = sfx * y[i];
+    }
+#pragma unroll
+    for (int i = KW - 1; i >= 0; --i) {
+        const double tt = pk[i] * sfx;
+        if (keep) m_t[(size_t)(e0 + i) * TILE + lane] = (1.0 + tt) / (1.0 - tt);
+        sfx = sfx * x[i];
+    }
 }
 
 // Closing block of the generic variable kernels: the ballot of the wave's

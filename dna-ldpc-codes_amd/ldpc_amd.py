@@ -76,7 +76,7 @@ class LdpcError(RuntimeError):
 
 # ldpc_schedule flag bits (include/ldpc_amd.h LDPC_SCHED_*) by keyword
 SCHED_FLAGS = {"nontemporal": 1 << 0, "continuous": 1 << 3, "msa_compressed": 1 << 4, "resident": 1 << 5,
-               "split_syndrome": 1 << 6, "handover": 1 << 7, "first_from_prior": 1 << 12, "lr_table": 1 << 13,
+               "split_syndrome": 1 << 6, "handover": 1 << 7, "fuse_row_block": 1 << 8, "first_from_prior": 1 << 12, "lr_table": 1 << 13,
                "debug_no_drain": 1 << 14, "debug_bad_lane": 1 << 15}
 SCHED_FIELDS = ("group_tiles", "var_cpw", "pool_tiles", "poll_every", "syn_blocks")
 
@@ -620,6 +620,8 @@ class Engine:
         self.syndrome_split = bool(f & SCHED_FLAGS["split_syndrome"])  # multi-block continuous-mode syndrome
         self.first_from_prior = bool(f & SCHED_FLAGS["first_from_prior"])
         self.handover = bool(f & SCHED_FLAGS["handover"])  # resident pool: refill during a codeword's last update
+        # resident BP pool: one row block's check update runs inside the variable kernel (k_var_bp_fused)
+        self.fused_row_block = bool(f & SCHED_FLAGS["fuse_row_block"])
 
     def decode(self, d_in, in_kind: int, B: int, max_iter: int, d_hard=None, d_post=None, post_kind=POST_LLR,
                d_iters=None, d_valid=None):

@@ -102,6 +102,12 @@ enum {
                                            last syndrome (the valid flag) follows in the next check: max_iter
                                            instead of max_iter + 1 steps per codeword that does not converge
                                            (default on; off elsewhere) */
+    LDPC_SCHED_FUSE_ROW_BLOCK = 1 << 8, /* resident pool on (8,72)-regular graphs, BP, var_cpw at its default:
+                                           when one of the 8 row blocks of M / 8 rows holds every column
+                                           exactly once, the variable kernel runs one workgroup per row of that
+                                           block, keeps the block's variable->check messages in LDS and
+                                           finishes the rows' check update itself; the check kernel skips
+                                           those rows' messages (default on; off elsewhere) */
     LDPC_SCHED_FIRST_FROM_PRIOR = 1 << 12, /* single-fill BP decodes: the first check derives its messages
                                               from the prior instead of E stored copies (default on) */
     LDPC_SCHED_LR_TABLE = 1 << 13,      /* ldpc_decode, BP (host exp) and min-sum: LLR batches on a k * unit
