@@ -378,6 +378,9 @@ int Engine::init(const HostGraph* graph, int dev, int algorithm, int64_t chunk, 
     if (chunk <= 0) LDPC_HIP(hipMemGetInfo(&fr, &tot));
     p = plan_engine(*g, algo, chunk, sched, fr);
     if (p.error) { set_error(p.error); return LDPC_ERR_ARG; }
+    // k_var_bp_fused addresses a tile's messages through a buffer resource:
+    // 32-bit byte offsets over E * 512 bytes
+    if (g->E * (int64_t)(dev::TILE * sizeof(double)) > 0x7fffffff) p.fuse_block = -1;
 
     if ((rc = dg.build(*g, p.msa_c))) return rc;
     if (p.cont && (rc = lp.build(p, g->N))) return rc;
@@ -570,7 +573,7 @@ int Engine::launch_var(double* scratch, int64_t t0, unsigned gt, double* pt, con
         if (t0 != 0 || timing) { set_error("fused row block: bad state"); return LDPC_ERR_ARG; }
         const dim3 grid((unsigned)(M / 8), gt);
         with_bools([&](auto PC) {
-            rc = launch(kc, (k_var_bp_fused<kFuseWaves, kFuseCpw, PC()>), grid, dim3(64 * kFuseWaves), v2c, prior, hard,
+            rc = launch(kc, (k_var_bp_fused<kFuseWaves, kFuseWindow, PC()>), grid, dim3(64 * kFuseWaves), v2c, prior, hard,
                         active, dg.col_edge, dg.col_idx, pt, N, E, p.fuse_block * (M / 8), rf);
         }, pc);
     } else if (reg8) {

@@ -1009,53 +1009,41 @@ __global__ __launch_bounds__(256) void k_var_m(typename Msg<INPLACE>::in c2v, ty
                                                  xcd_block(blockIdx.x, gridDim.x), rf);
 }
 
-// ---------------------------------------------------------------------------
-// Resident pool, BP on an (8, 72)-regular code, fused row block
-// (EnginePlan::fuse_block = a: rows [row0, row0 + M / 8) hold every column
-// exactly once).  One workgroup per (row of that block, tile): the row's 72
-// columns belong to this workgroup alone, so it runs their variable phase --
-// W waves x KW = 72 / W columns, CPW at a time, the arithmetic and stores of
-// var_m_block<false, 8, false, true, ., true, PC> (var_column and its
-// companions) -- and keeps the row's own variable->check messages in LDS
-// instead of storing them.  After one barrier it finishes the row's check
-// update from them: check_bp_compute's operations in its order (prefix
-// products from slot 0 up, suffix from slot 71 down, lr = (1 + t) / (1 - t)),
-// each wave for its own KW edges, recomputing the prefix before and the
-// suffix behind them; the results go to the edges in place, where the
-// next variable phase reads them.  k_check_bp_skip leaves those rows'
-// messages alone.  So the block's d never reaches memory: the next check
-// moves 7/8 of its message bytes.
-// In place without hazards across workgroups: every edge of a column is read
-// and written by the workgroup that owns the column, and the row's lr stores
-// follow the barrier, after every lr load of the workgroup.
-// Every condition in front of the barrier is per tile (workgroup-uniform).
-// grid (M / 8, tiles), block 64 * W.
-// W = 8, CPW = 3 (kFuseWaves, kFuseCpw): 24 outstanding 512-B loads per wave
-// and round, 112 VGPRs, 36 KB LDS, no scratch, 4 waves per SIMD.  The fastest
-// of the geometries timed (4 x 2, 4 x 3, 6 x 2, 6 x 3, 8 x 3); their
-// resources and times are in profiles/r14/README.md.
-// ---------------------------------------------------------------------------
-constexpr int kFuseWaves = 8, kFuseCpw = 3;
-template <int W, int CPW, bool PC>
-__global__ __launch_bounds__(64 * W) void k_var_bp_fused(double* msg, double* __restrict__ prior,
-                                                         uint64_t* __restrict__ hard,
-                                                         const uint64_t* __restrict__ active,
-                                                         const int32_t* __restrict__ col_edge,
-                                                         const int32_t* __restrict__ col_idx, double* post, int32_t N,
-                                                         int64_t E, int32_t row0, Refill rf)
+// Raw buffer resource over [base, base + bytes) (gfx9 data format, no
+// swizzle, stride 0).  A wave's gathers and scatters then take a
+// wave-uniform byte offset in an SGPR (soffset) and one shared per-lane
+// offset in a VGPR: no per-edge 64-bit address arithmetic on the VALU.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kBufNT = 2;  // cache-policy bits of a buffer access: nt (gfx950), as __builtin_nontemporal_store
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, uint64_t bytes)
 {
-    constexpr int DC = 72, DV = 8, KW = DC / W;
-    static_assert(DC % W == 0 && KW % CPW == 0, "the row's columns split evenly over the waves and their rounds");
-    __shared__ double sd[DC][TILE];  // the row's d, slot k = the column's position in the row
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0,
+                                            (int)(bytes < 0x7fffffffull ? bytes : 0x7fffffffull), 0x00020000);
+}
+
+// The fused row block's kernel (k_var_bp_fused, below its row function):
+// waves per workgroup, and the columns a wave of its plain path has in flight.
+constexpr int kFuseWaves = 8, kFuseWindow = 4;
+constexpr int kFuseDc = 72;
+
+// One tile's row: the W waves' columns, WIN of them in flight per wave, then
+// the barrier and the row's check update.  RARE = false (no lane of the tile
+// is refilled, finished or in its final update): frm, fm and lastm are the
+// constant 0, so the refill, finished-output and hand-over arms and their lane
+// state drop out of the instantiation.  sd: the workgroup's LDS.
+template <int W, int WIN, bool PC, bool RARE>
+__device__ __forceinline__ void var_bp_fused_row(double (&sd)[kFuseDc][TILE], double* msg, double* __restrict__ prior,
+                                                 uint64_t* __restrict__ hard, const int32_t* __restrict__ col_edge,
+                                                 const int32_t* __restrict__ col_idx, double* post, int32_t N,
+                                                 int64_t E, int32_t row, int64_t t, uint64_t act, uint64_t frm_,
+                                                 uint64_t fm_, uint64_t lastm_, const Refill& rf)
+{
+    constexpr int DC = kFuseDc, DV = 8, KW = DC / W;
+    static_assert(DC % W == 0 && WIN >= 1, "the row's columns split evenly over the waves");
     const int lane = lane_id(), w = wave_id();
-    const int64_t t = blockIdx.y;
-    const int32_t row = row0 + (int32_t)xcd_block(blockIdx.x, gridDim.x);
-    const uint64_t act = active[t];
-    const uint64_t frm = rf.fresh[t];
+    const uint64_t frm = RARE ? frm_ : 0ull, fm = RARE ? fm_ : 0ull, lastm = RARE ? lastm_ : 0ull;
     const uint64_t touched = act | frm;
-    const uint64_t fm = rf.fin ? rf.fin[t] : 0ull;
-    const uint64_t lastm = rf.last ? rf.last[t] : 0ull;
-    if (touched == 0 && fm == 0) return;  // per tile
     const bool live = (act >> lane) & 1ull;
     const bool fr = (frm >> lane) & 1ull;
     const bool fl = (fm >> lane) & 1ull;
@@ -1066,7 +1054,11 @@ __global__ __launch_bounds__(64 * W) void k_var_bp_fused(double* msg, double* __
         fb = rf.fin_b[t * TILE + lane];
         fn = rf.fin_n[t * TILE + lane];
     }
-    double* m_t = msg + (size_t)t * E * TILE;  // the tile's messages (a scalar base: the lane goes into the offset)
+    // the tile's messages through a buffer resource: the edge's byte offset
+    // is wave-uniform (soffset), the lane's a VGPR shared by every access
+    // (E * 512 < 2^31: Engine::create keeps larger codes off this kernel)
+    const auto rm = buf_rsrc(msg + (size_t)t * E * TILE, (uint64_t)E * TILE * 8);
+    const int lo = lane * 8;
     const int k0 = w * KW;
     const int32_t e0 = row * DC + k0;  // the wave's first edge of the row
     bool bad_in = false;
@@ -1079,74 +1071,66 @@ __global__ __launch_bounds__(64 * W) void k_var_bp_fused(double* msg, double* __
     const int64_t lb = ls ? rf.pend_b[t * TILE + lane] : 0;
     const bool lok = out_ok(lb, rf), fok = out_ok(fb, rf);
     const bool keep = line_occupied(touched, lane) || fr || live;  // whole-line stores, as var_m_block
+    // A rolling window of WIN columns: column k's loads are issued when
+    // column k - WIN has been stored, so the wave has loads in flight from its
+    // first column to its last (in rounds of WIN columns -- all loads, then
+    // all arithmetic, then all stores -- the workgroups of a CU, which start
+    // together, alternate between loading and storing together).
+    int32_t j[KW], eid[KW][DV];
+    double l[KW][DV], pv[KW], xin[KW];
+    int8_t kin[KW];
 #pragma unroll
-    for (int r = 0; r < KW; r += CPW) {
-        int32_t j[CPW], eid[CPW][DV];
+    for (int k = 0; k < KW; ++k) j[k] = col_idx[e0 + k];
+    auto issue = [&](int k) __attribute__((always_inline)) {
 #pragma unroll
-        for (int c = 0; c < CPW; ++c) j[c] = col_idx[e0 + r + c];
-#pragma unroll
-        for (int c = 0; c < CPW; ++c)
-#pragma unroll
-            for (int s = 0; s < DV; ++s) eid[c][s] = col_edge[(size_t)j[c] * DV + s];
-        double l[CPW][DV], pv[CPW], xin[CPW];
-        int8_t kin[CPW];
+        for (int s = 0; s < DV; ++s) eid[k][s] = col_edge[(size_t)j[k] * DV + s];
         if (fr) {
-#pragma unroll
-            for (int c = 0; c < CPW; ++c) {
-                if constexpr (PC) kin[c] = rf.in_code[rb + j[c]];
-                else xin[c] = rf.in[rb + j[c]];
-            }
+            if constexpr (PC) kin[k] = rf.in_code[rb + j[k]];
+            else xin[k] = rf.in[rb + j[k]];
         }
         if (live) {
+            pv[k] = prior_at<PC>(prior, rf, ((size_t)t * N + j[k]) * TILE + lane);
 #pragma unroll
-            for (int c = 0; c < CPW; ++c) {
-                pv[c] = prior_at<PC>(prior, rf, ((size_t)t * N + j[c]) * TILE + lane);
-#pragma unroll
-                for (int s = 0; s < DV; ++s) l[c][s] = m_t[(size_t)eid[c][s] * TILE + lane];
-            }
+            for (int s = 0; s < DV; ++s)
+                l[k][s] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rm, lo, eid[k][s] * (TILE * 8), 0));
         }
-        if constexpr (PC) {
-            if (fr) {
+    };
 #pragma unroll
-                for (int c = 0; c < CPW; ++c) xin[c] = rf.ptab[kin[c] + kCodeBias];
-            }
+    for (int k = 0; k < WIN && k < KW; ++k) issue(k);
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+        if constexpr (PC) {
+            if (fr) xin[k] = rf.ptab[kin[k] + kCodeBias];
         }
         if (lastm != 0) {  // hand-over (var_m_block): final updates, outputs and the second ballot plane
-#pragma unroll
-            for (int c = 0; c < CPW; ++c) {
-                const uint64_t hwf = __ballot(var_column_final<false, DV>(ls, pv[c], l[c], lok, rf, lb, N, j[c]));
-                if (lane == 0) rf.hard_fin[(size_t)t * N + j[c]] = hwf;
-                if (ls && lok) store_fin_hard<1>(rf, &hwf, lb, N, j[c], lane);
-            }
+            const uint64_t hwf = __ballot(var_column_final<false, DV>(ls, pv[k], l[k], lok, rf, lb, N, j[k]));
+            if (lane == 0) rf.hard_fin[(size_t)t * N + j[k]] = hwf;
+            if (ls && lok) store_fin_hard<1>(rf, &hwf, lb, N, j[k], lane);
         }
         if (fl && fok) {  // finished codeword: hard bits of its exit (ballots before this step's update)
+            const uint64_t hw = hard[(size_t)t * N + j[k]];
+            store_fin_hard<1>(rf, &hw, fb, N, j[k], lane);
+        }
+        const size_t pj = ((size_t)t * N + j[k]) * TILE + lane;
+        if (fl && fok && rf.post_out) var_column_fin_post<false, PC>(rf, prior, post, pj, (size_t)fb * N + j[k], fn);
+        bool h;
+        double dv[DV], np;
+        var_column<false, DV, PC>(live, fr, ls, pv[k], xin[k], l[k], rf, post, pj, dv, np, h);
+        if (fr) {
+            if constexpr (PC) rf.pcode[pj] = kin[k];
+            else prior[pj] = np;
+        }
+        const int32_t ea = e0 + k;  // the column's edge in this row: to LDS (a wave-uniform choice per slot)
+        if (keep) {
 #pragma unroll
-            for (int c = 0; c < CPW; ++c) {
-                const uint64_t hw = hard[(size_t)t * N + j[c]];
-                store_fin_hard<1>(rf, &hw, fb, N, j[c], lane);
+            for (int s = 0; s < DV; ++s) {
+                if (eid[k][s] == ea) sd[k0 + k][lane] = dv[s];
+                else
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, dv[s]), rm, lo, eid[k][s] * (TILE * 8), 0);
             }
         }
-#pragma unroll
-        for (int c = 0; c < CPW; ++c) {
-            const size_t pj = ((size_t)t * N + j[c]) * TILE + lane;
-            if (fl && fok && rf.post_out) var_column_fin_post<false, PC>(rf, prior, post, pj, (size_t)fb * N + j[c], fn);
-            bool h;
-            double dv[DV], np;
-            var_column<false, DV, PC>(live, fr, ls, pv[c], xin[c], l[c], rf, post, pj, dv, np, h);
-            if (fr) {
-                if constexpr (PC) rf.pcode[pj] = kin[c];
-                else prior[pj] = np;
-            }
-            const int32_t ea = e0 + r + c;  // the column's edge in this row: to LDS (a wave-uniform choice per slot)
-            if (keep) {
-#pragma unroll
-                for (int s = 0; s < DV; ++s) {
-                    if (eid[c][s] == ea) sd[k0 + r + c][lane] = dv[s];
-                    else m_t[(size_t)eid[c][s] * TILE + lane] = dv[s];
-                }
-            }
-            merge_touched(hard, t, N, j[c], touched, h, lane);
-        }
+        merge_touched(hard, t, N, j[k], touched, h, lane);
+        if (k + WIN < KW) issue(k + WIN);
     }
     if (lastm != 0 && ls && !lok) lane_fault(rf.fault, kFaultOutput, t * TILE + lane);
     if (fl && !fok) lane_fault(rf.fault, kFaultOutput, t * TILE + lane);
@@ -1177,12 +1161,72 @@ __global__ __launch_bounds__(64 * W) void k_var_bp_fused(double* msg, double* __
 #pragma unroll
         for (int i = KW - 1; i >= 0; --i) sfx = sfx * y[i];
     }
+    double lr[KW];
 #pragma unroll
     for (int i = KW - 1; i >= 0; --i) {
         const double tt = pk[i] * sfx;
-        if (keep) m_t[(size_t)(e0 + i) * TILE + lane] = (1.0 + tt) / (1.0 - tt);
+        lr[i] = (1.0 + tt) / (1.0 - tt);
         sfx = sfx * x[i];
     }
+    if (keep) {
+#pragma unroll
+        for (int i = KW - 1; i >= 0; --i)
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lr[i]), rm, lo, (e0 + i) * (TILE * 8), 0);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Resident pool, BP on an (8, 72)-regular code, fused row block
+// (EnginePlan::fuse_block = a: rows [row0, row0 + M / 8) hold every column
+// exactly once).  One workgroup per (row of that block, tile): the row's 72
+// columns belong to this workgroup alone, so it runs their variable phase --
+// W waves x 72 / W columns, the arithmetic and stores of
+// var_m_block<false, 8, false, true, ., true, PC> (var_column and its
+// companions) -- and keeps the row's own variable->check messages in LDS
+// instead of storing them.  After one barrier it finishes the row's check
+// update from them: check_bp_compute's operations in its order (prefix
+// products from slot 0 up, suffix from slot 71 down, lr = (1 + t) / (1 - t)),
+// each wave for its own 72 / W edges, recomputing the prefix before and the
+// suffix behind them; the results go to the edges in place, where the next
+// variable phase reads them.  k_check_bp_skip leaves those rows' messages
+// alone.  So the block's d never reaches memory: the next check moves 7/8 of
+// its message bytes.
+// Two paths, chosen per tile (workgroup-uniform, as is every condition in
+// front of the barrier): a tile without a refilled, finished or last lane --
+// 49 steps of 50 per lane -- takes the plain path with kFuseWindow columns in
+// flight per wave, every other tile the path with all arms, one column at a
+// time (var_bp_fused_row<.., RARE>).
+// In place without hazards across workgroups: every edge of a column is read
+// and written by the workgroup that owns the column, and the row's lr stores
+// follow the barrier, after every lr load of the workgroup.
+// grid (M / 8, tiles), block 64 * W.
+// W = 8, window 4 (kFuseWaves, kFuseWindow): 104 VGPRs, 36 KB LDS, no
+// scratch, 4 waves per SIMD, two workgroups per CU.  The geometries, windows
+// and the last-wave row finish that were timed, with their resources:
+// profiles/r15/README.md.
+// ---------------------------------------------------------------------------
+template <int W, int WIN, bool PC>
+__global__ __launch_bounds__(64 * W) void k_var_bp_fused(double* msg, double* __restrict__ prior,
+                                                         uint64_t* __restrict__ hard,
+                                                         const uint64_t* __restrict__ active,
+                                                         const int32_t* __restrict__ col_edge,
+                                                         const int32_t* __restrict__ col_idx, double* post, int32_t N,
+                                                         int64_t E, int32_t row0, Refill rf)
+{
+    __shared__ double sd[kFuseDc][TILE];  // the row's d, slot k = the column's position in the row
+    const int64_t t = blockIdx.y;
+    const int32_t row = row0 + (int32_t)xcd_block(blockIdx.x, gridDim.x);
+    const uint64_t act = active[t];
+    const uint64_t frm = rf.fresh[t];
+    const uint64_t fm = rf.fin ? rf.fin[t] : 0ull;
+    const uint64_t lastm = rf.last ? rf.last[t] : 0ull;
+    if ((act | frm) == 0 && fm == 0) return;  // per tile
+    if ((frm | fm | lastm) != 0)
+        var_bp_fused_row<W, 1, PC, true>(sd, msg, prior, hard, col_edge, col_idx, post, N, E, row, t, act, frm, fm, lastm,
+                                         rf);
+    else
+        var_bp_fused_row<W, WIN, PC, false>(sd, msg, prior, hard, col_edge, col_idx, post, N, E, row, t, act, 0ull, 0ull,
+                                            0ull, rf);
 }
 
 // Closing block of the generic variable kernels: the ballot of the wave's
@@ -1824,19 +1868,6 @@ __global__ __launch_bounds__(256) void k_var_gr_cont(typename Msg<INPLACE>::in c
     if (fl && !fok) lane_fault(rf.fault, kFaultOutput, t * TILE + lane);
     asm volatile("" : "+v"(bad_v));
     if (bad_v) lane_fault(rf.fault, kFaultRefill, t * TILE + lane);
-}
-
-// Raw buffer resource over [base, base + bytes) (gfx9 data format, no
-// swizzle, stride 0).  A wave's gathers and scatters then take a
-// wave-uniform byte offset in an SGPR (soffset) and one shared per-lane
-// offset in a VGPR: no per-edge 64-bit address arithmetic on the VALU.
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr int kBufNT = 2;  // cache-policy bits of a buffer access: nt (gfx950), as __builtin_nontemporal_store
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, uint64_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0,
-                                            (int)(bytes < 0x7fffffffull ? bytes : 0x7fffffffull), 0x00020000);
 }
 
 // ---------------------------------------------------------------------------
