@@ -17,13 +17,12 @@
  * keeping the reference's fp64 operation order exactly (sequential left-
  * associative products/sums per row and per column, NaN->1 guards, tie rules).
  *
- * Parity pinning (see DESIGN.md "Oracle"): the reference's dec.cpp cannot be
- * compiled here without a stand-in for Intel MKL's mkl_vsl.h (rand.h:8) and the
- * MSVC-only _isnan (dec.cpp:676,687), so the BP/MSA arithmetic of this oracle
- * is pinned only by the reference's own fixtures (272 true codewords, genie
- * check) -- "parity partially unpinned" for non-converging trajectories.
- * The graph loader and syndrome ARE pinned against the reference's own
- * mod2sparse.cpp/rcode.cpp/check.cpp, compiled unmodified into oracle/_ref/.
+ * Parity pinning (see DESIGN.md "Oracle"): the reference's own dec.cpp,
+ * compiled unmodified into oracle/_ref/librefdec.so (ref_dec_harness.cpp),
+ * pins the BP, min-sum, Gallager and quantised min-sum arithmetic of this
+ * oracle bit for bit (tests/test_reference_decoder.py and the recorded
+ * tests/golden/refdec_goldens.npz); the graph loader and syndrome are pinned
+ * against mod2sparse.cpp/rcode.cpp/check.cpp in oracle/_ref/libref.so.
  *
  * Build: oracle/Makefile  (gcc -O2 -ffp-contract=off, no fast-math).
  */

@@ -7,7 +7,8 @@ this module, and only as the checker / CPU baseline.  The product
 Wraps oracle/liboracle.so (the C restatement of LDPC_dec/ldpc/dec.cpp:583-694,
 1216-1678, check.cpp:28-45, rcode.cpp:54-85; see ldpc_oracle.c) and, when
 built, oracle/_ref/libref.so (the reference's own unmodified loader +
-syndrome sources; see ref_harness.cpp).
+syndrome sources; see ref_harness.cpp) and oracle/_ref/librefdec.so (the
+reference's own unmodified dec.cpp; see ref_dec_harness.cpp).
 """
 from __future__ import annotations
 
@@ -201,3 +202,120 @@ class RefGraph:
         pchk = np.zeros(self.M, np.uint8)
         c = RefGraph._lib.ref_check(_p(dblk), _p(pchk))
         return c, pchk
+
+
+# ---------------------------------------------------------------------------
+# oracle/_ref/librefdec.so: the reference's own decoders (dec.cpp, unmodified)
+# ---------------------------------------------------------------------------
+def refdec_available() -> bool:
+    return os.path.exists(os.path.join(_HERE, "_ref", "librefdec.so"))
+
+
+class RefDecoder:
+    """The reference's Run_* decoders on the reference's own matrix (one per
+    process: a new RefDecoder replaces the matrix of the previous one).  Every
+    decode takes [B][N] and returns (hard u8[B][N], post, iters i32[B],
+    valid u8[B]) like OracleGraph's batch calls."""
+
+    _lib = None
+
+    @staticmethod
+    def _load_lib():
+        if RefDecoder._lib is None:
+            L = C.CDLL(os.path.join(_HERE, "_ref", "librefdec.so"))
+            ip = C.POINTER(C.c_int)
+            L.refdec_load.argtypes = [C.c_char_p, ip, ip, ip, ip]
+            L.refdec_ties.restype = C.c_int64
+            L.refdec_tie_queue.argtypes = [C.c_void_p, C.c_int64]
+            L.refdec_tie_queue_state.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            L.refdec_bp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, ip]
+            L.refdec_msa.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, ip]
+            L.refdec_gallager.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, ip]
+            L.refdec_quantise.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_int, C.c_void_p]
+            L.refdec_qmsa.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, ip,
+                                      C.POINTER(C.c_int64)]
+            RefDecoder._lib = L
+        return RefDecoder._lib
+
+    def __init__(self, path: str):
+        v = [C.c_int() for _ in range(4)]
+        self._L = RefDecoder._load_lib()
+        self._L.refdec_load(path.encode(), *[C.byref(x) for x in v])
+        self.M, self.N, self.dv, self.dc = (x.value for x in v)
+
+    def _out(self, B, post_dtype):
+        return (np.zeros((B, self.N), np.uint8), np.zeros((B, self.N), post_dtype), np.zeros(B, np.int32),
+                np.zeros(B, np.uint8))
+
+    def _in(self, x, dtype):
+        x = np.ascontiguousarray(x, dtype=dtype)
+        if x.ndim != 2 or x.shape[1] != self.N:
+            raise ValueError(f"input must have shape [B][{self.N}]")
+        return x
+
+    def ties(self) -> int:
+        """rand_int calls so far (dec.cpp:1273, :1647)."""
+        return int(self._L.refdec_ties())
+
+    def bp(self, lratio: np.ndarray, max_iter: int):
+        """Run_Belief_Propagation_Decoder on likelihood ratios; post = the posterior ratio."""
+        x = self._in(lratio, np.float64)
+        hard, post, iters, valid = self._out(len(x), np.float64)
+        for b in range(len(x)):
+            v = C.c_int()
+            iters[b] = self._L.refdec_bp(_p(x[b]), max_iter, _p(hard[b]), _p(post[b]), C.byref(v))
+            valid[b] = v.value
+        return hard, post, iters, valid
+
+    def msa(self, llr: np.ndarray, max_iter: int):
+        """Run_MSA_Decoder_INF; post = L."""
+        x = self._in(llr, np.float64)
+        hard, post, iters, valid = self._out(len(x), np.float64)
+        for b in range(len(x)):
+            v = C.c_int()
+            iters[b] = self._L.refdec_msa(_p(x[b]), max_iter, _p(hard[b]), _p(post[b]), C.byref(v))
+            valid[b] = v.value
+        return hard, post, iters, valid
+
+    def gallager(self, recv: np.ndarray, kind: int, max_iter: int):
+        """Run_Gallager_Decoder, kind 0 / 1 / 2 = A / B1 / B2, recv in {-1, +1}; post is None."""
+        x = self._in(recv, np.int32)
+        hard, _, iters, valid = self._out(len(x), np.int32)
+        for b in range(len(x)):
+            v = C.c_int()
+            iters[b] = self._L.refdec_gallager(_p(x[b]), kind, max_iter, _p(hard[b]), C.byref(v))
+            valid[b] = v.value
+        return hard, None, iters, valid
+
+    def quantise(self, x: np.ndarray, precision: int, step: float, beta: int = 0):
+        """Set_MSA + Cal_MSA_Q(x, 0) per value."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.zeros(x.shape, np.int32)
+        self._L.refdec_quantise(_p(x), x.size, precision, step, beta, _p(out))
+        return out
+
+    def qmsa(self, llr: np.ndarray, max_iter: int, precision: int, step: float, beta: int, tie_bits=None):
+        """Set_MSA, Cal_MSA_Q, Run_MSA_Decoder; post = L_Q (int32).  Returns a
+        fifth array: rand_int calls per word.  Ties decide 0, or take their bits
+        from tie_bits[b] (a sequence of 0/1 per word) in call order; a word whose
+        queue ran short or was not used up raises."""
+        x = self._in(llr, np.float64)
+        hard, post, iters, valid = self._out(len(x), np.int32)
+        ties = np.zeros(len(x), np.int64)
+        for b in range(len(x)):
+            v, t = C.c_int(), C.c_int64()
+            q = None if tie_bits is None else np.ascontiguousarray(tie_bits[b], dtype=np.uint8)
+            if q is not None:
+                self._L.refdec_tie_queue(_p(q), q.size)
+            try:
+                iters[b] = self._L.refdec_qmsa(_p(x[b]), precision, step, beta, max_iter, _p(hard[b]), _p(post[b]),
+                                               C.byref(v), C.byref(t))
+                if q is not None:
+                    left, under = C.c_int64(), C.c_int64()
+                    self._L.refdec_tie_queue_state(C.byref(left), C.byref(under))
+                    if left.value or under.value:
+                        raise ValueError(f"word {b}: tie queue {left.value} unread, {under.value} missing")
+            finally:
+                self._L.refdec_tie_queue(None, 0)
+            valid[b], ties[b] = v.value, t.value
+        return hard, post, iters, valid, ties

@@ -7,8 +7,8 @@
 //   :502-604, mulvec :855-881), check.cpp (check :28-45), intio.cpp, open.cpp,
 //   alloc.cpp, mod2dense.cpp, mod2convert.cpp.
 // None of those files needs Intel MKL or MSVC-only functions, so they build
-// with plain g++ and no stand-ins.  dec.cpp (BP/MSA arithmetic) does need them
-// (rand.h:8 mkl_vsl.h; dec.cpp:676,687 _isnan) and is NOT built.
+// with plain g++ and no stand-ins.  dec.cpp (the decoders) is built into its
+// own library, oracle/_ref/librefdec.so (ref_dec_harness.cpp).
 //
 // Used by tests/test_graph.py to pin the oracle's and the product's CSR/CSC
 // edge ordering and syndrome against the reference's own linked lists.
