@@ -7,12 +7,14 @@ with g++ into pytest's tmp_path.
 
 The schedule runs only in the resident pool, for BP, on an (8, 72)-regular
 code with such a block, with var_cpw at its default and the flag not turned
-off; everything else keeps fuse_block = -1."""
+off; everything else keeps fuse_block = -1.  The codes of
+fused_block_cases (the whole block is block 7, 3 or 1) give that block."""
 import os
 import subprocess
 
 import numpy as np
 
+import fused_block_cases
 from conftest import PCHK, ROOT
 from real_llr_cases import regular_rows_permuted
 from test_gpu_parity import _write_pchk
@@ -48,8 +50,18 @@ def test_fuse_plan(tmp_path):
         seen = [c for r, c in zip(rows3, cols3) if r // 4 == a]
         assert len(set(seen)) < len(seen)
     _write_pchk(tmp_path / "perm4.pchk", Mp, Np, rows3, cols3)
+    # block a alone holds every column once, a = 7, 3, 1 (Q = 4) and 3 (Q = 12): the codes the GPU decodes
+    # (tests/test_fused_block_position_gpu.py), from the same builder and seeds
+    placed = []
+    for name, (Q, a, _) in fused_block_cases.CODES.items():
+        Mb, Nb, rows4, cols4 = fused_block_cases.code(name)
+        assert (Mb, Nb) == (8 * Q, 72 * Q)
+        _write_pchk(tmp_path / f"{name}.pchk", Mb, Nb, rows4, cols4)
+        placed.append((name, Mb, Nb, a))
+    assert [(n, a) for n, _, _, a in placed] == [("blk7_4", 7), ("blk3_4", 3), ("blk1_4", 1), ("blk3_12", 3)]
     r = subprocess.run([exe, f"dna={PCHK}", "rs7", f"reg4={tmp_path / 'reg4.pchk'}", f"swap4={tmp_path / 'swap4.pchk'}",
-                        f"perm4={tmp_path / 'perm4.pchk'}"], capture_output=True, text=True)
+                        f"perm4={tmp_path / 'perm4.pchk'}"] + [f"{n}={tmp_path / (n + '.pchk')}" for n, _, _, _ in placed],
+                       capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     want = [
         _line("dna", 2048, 18432, 0, 0),
@@ -57,5 +69,9 @@ def test_fuse_plan(tmp_path):
         _line("reg4", 32, 288, 0, 0),
         _line("swap4", 32, 288, 1, 1),
         _line("perm4", 32, 288, -1, -1),
+        _line("blk7_4", 32, 288, 7, 7),
+        _line("blk3_4", 32, 288, 3, 3),
+        _line("blk1_4", 32, 288, 1, 1),
+        _line("blk3_12", 96, 864, 3, 3),
     ]
     assert r.stdout.splitlines() == want
