@@ -93,7 +93,7 @@ def pad_align(seqs: Sequence[str]) -> List[Tuple[int, str]]:
 
 @dataclass
 class LlrResult:
-    llr: np.ndarray                # [2*PAYLOAD_NT][S] float64 (soft file i+1 = row i)
+    llr: np.ndarray                # [2*payload_nt][S] float64 (soft file i+1 = row i)
     int_mask: np.ndarray           # same shape, uint8: 1 = int 0 in the reference
     kind: np.ndarray               # [S] int32 strand classification
     n_reads_valid: int = 0
@@ -102,7 +102,7 @@ class LlrResult:
     erased: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int64))  # strands with no LLRs
     # the count differences: llr == codes * unit exactly (decoder.py:297-314);
     # None when some |count difference| > 127 (no int8 code)
-    codes: Optional[np.ndarray] = None  # [2*PAYLOAD_NT][S] int8
+    codes: Optional[np.ndarray] = None  # [2*payload_nt][S] int8
     unit: float = 0.0                   # ln((1-eps)/eps)
     n_align_pairs: int = 0              # read-to-centre alignments of align_fn="star"
     t_align_s: float = 0.0              # time spent in the aligner
@@ -384,7 +384,7 @@ class LlrPlan:
     """Host classification handed to ldpc_dna_llr."""
     kind: np.ndarray      # [S] int32
     row_ptr: np.ndarray   # [S+1] int64
-    rows: np.ndarray      # [max(R,1)][PAYLOAD_NT] uint8
+    rows: np.ndarray      # [max(R,1)][payload_nt] uint8
     row_q: np.ndarray     # [max(R,1)] int32
     n_reads_valid: int
     n_pairs: int
@@ -396,7 +396,7 @@ class LlrPlan:
 
 def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int],
              align_fn: Optional[AlignFn] = None, device: int = 0, strands: Optional[np.ndarray] = None,
-             distance_fn=None, align_host: Optional[bool] = None) -> LlrPlan:
+             distance_fn=None, align_host: Optional[bool] = None, payload_nt: int = PAYLOAD_NT) -> LlrPlan:
     """Group and classify the reads (decoder.py:103-497 control flow).
     Pairwise distances of ragged strands come from the GPU
     (`distance_fn` defaults to edit_distance on `device`).  align_fn is a
@@ -404,7 +404,11 @@ def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int
     of all ragged strands then go to the built-in aligner in one batched call
     (star_align_groups on `device`; on the CPU with align_host=True, which is
     also what a caller gets who keeps the distances off the GPU with a
-    distance_fn and leaves align_host None)."""
+    distance_fn and leaves align_host None).  payload_nt: the payload length
+    of a strand in nucleotides (half the number of codewords)."""
+    nt = int(payload_nt)
+    if nt < 1:
+        raise ValueError("payload_nt must be at least 1")
     if isinstance(align_fn, str) and align_fn != "star":
         raise ValueError(f"unknown aligner {align_fn!r} (a callable or 'star')")
     if align_host is None:
@@ -429,12 +433,12 @@ def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int
 
     kind = np.zeros(S, np.int32)
     all_full = np.ones(S, bool)
-    np.logical_and.at(all_full, rpos, lens == PAYLOAD_NT)
+    np.logical_and.at(all_full, rpos, lens == nt)
     single = cnt == 1
     first_len = np.zeros(S, np.int64)
     first_len[cnt > 0] = lens[start[:-1][cnt > 0]]
-    kind[single & (first_len < PAYLOAD_NT)] = KIND_SHORT
-    kind[single & (first_len >= PAYLOAD_NT)] = KIND_COUNT
+    kind[single & (first_len < nt)] = KIND_SHORT
+    kind[single & (first_len >= nt)] = KIND_COUNT
     multi = cnt > 1
     kind[multi & all_full] = KIND_COUNT
     ragged = np.nonzero(multi & ~all_full)[0]
@@ -479,7 +483,7 @@ def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int
         for (s, cand, cq), recs in zip(todo, records):
             aligned, aq, err, eq = [], [], [], []
             for order, a in recs:  # decoder.py:195-214
-                if len(a) != PAYLOAD_NT:
+                if len(a) != nt:
                     err.append(a[-1] if a else "")
                     eq.append(int(cq[order]))
                     continue
@@ -493,7 +497,7 @@ def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int
                 kind[s] = KIND_ALIGN_FAILED
                 rows_of[s] = (err, eq)
 
-    # rows: PAYLOAD_NT bytes each (kinds 2/3: byte 0 = last base)
+    # rows: nt bytes each (kinds 2/3: byte 0 = last base)
     row_count = np.zeros(S, np.int64)
     plain_count = (kind == KIND_COUNT) & ~np.isin(np.arange(S), list(rows_of.keys()))
     row_count[plain_count] = cnt[plain_count]
@@ -503,17 +507,17 @@ def plan_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int
     row_ptr = np.zeros(S + 1, np.int64)
     row_ptr[1:] = np.cumsum(row_count)
     R = int(row_ptr[-1])
-    rows = np.full((max(R, 1), PAYLOAD_NT), ord("-"), np.uint8)
+    rows = np.full((max(R, 1), nt), ord("-"), np.uint8)
     row_q = np.zeros(max(R, 1), np.int32)
 
-    # plain count strands: the reads' first PAYLOAD_NT bases, vectorised
+    # plain count strands: the reads' first nt bases, vectorised
     pc = np.nonzero(plain_count)[0]
     if len(pc):
         sel_reads = np.concatenate([np.arange(start[s], start[s + 1]) for s in pc])
         dst = np.concatenate([np.arange(row_ptr[s], row_ptr[s + 1]) for s in pc])
-        blob = np.frombuffer("".join(seqs[read_ids[r]][:PAYLOAD_NT] for r in sel_reads).encode("latin-1"),
+        blob = np.frombuffer("".join(seqs[read_ids[r]][:nt] for r in sel_reads).encode("latin-1"),
                              np.uint8)
-        rows[dst] = blob.reshape(-1, PAYLOAD_NT)
+        rows[dst] = blob.reshape(-1, nt)
         row_q[dst] = q_all[read_ids[sel_reads]]
     for s in np.nonzero(kind == KIND_SHORT)[0]:
         r = read_ids[start[s]]
@@ -576,23 +580,25 @@ def _native_check(mod, rc):
 
 
 def plan_llr_native(index_vals, seqs, quals, device: int = 0, host: bool = False,
-                    strands: Optional[np.ndarray] = None, align: bool = True, workspace_bytes: int = 0) -> LlrPlan:
+                    strands: Optional[np.ndarray] = None, align: bool = True, workspace_bytes: int = 0,
+                    payload_nt: int = PAYLOAD_NT) -> LlrPlan:
     """plan_llr(..., align_fn="star") in the library: ldpc_dna_plan on GPU
     `device`, or ldpc_dna_plan_host on one CPU thread (host=True); the same
     bytes either way.  index_vals None: `seqs` are raw reads, whose 16-nt
     prefix is decoded and dropped inside the call (split_reads).  seqs is a
     list of str or an already packed (buf, offsets, lengths) triple (_concat).
     align=False is align_fn=None.  The cnumerr histogram of raw reads is
-    plan.cnumerr_hist."""
+    plan.cnumerr_hist.  payload_nt: the payload length of a strand."""
     mod, L = _lib()
     buf, offs, lens, q, iv, sidx, n = _native_inputs(index_vals, seqs, quals, strands)
     S = len(sidx)
+    nt = int(payload_nt)
     kind = np.zeros(S, np.int32)
     row_ptr = np.zeros(S + 1, np.int64)
-    rows = np.full((max(n, 1), PAYLOAD_NT), ord("-"), np.uint8)
+    rows = np.full((max(n, 1), max(nt, 1)), ord("-"), np.uint8)
     row_q = np.zeros(max(n, 1), np.int32)
     stats = np.zeros(N_PLAN_STATS, np.int64)
-    head = (_p(buf), _p(offs), _p(lens), _p(q), n, None if iv is None else _p(iv), _p(sidx), S, PAYLOAD_NT,
+    head = (_p(buf), _p(offs), _p(lens), _p(q), n, None if iv is None else _p(iv), _p(sidx), S, nt,
             1 if align else 0)
     tail = (_p(kind), _p(row_ptr), _p(rows), _p(row_q), _p(stats))
     if host:
@@ -615,21 +621,24 @@ def _native_align(align_fn) -> bool:
 
 
 def build_llr_native(index_vals, seqs, quals, eps: float = 0.02, align: bool = True, device: int = 0,
-                     strands: Optional[np.ndarray] = None, workspace_bytes: int = 0):
+                     strands: Optional[np.ndarray] = None, workspace_bytes: int = 0,
+                     payload_nt: int = PAYLOAD_NT):
     """ldpc_dna_reads_llr: reads (raw when index_vals is None; a list of str or
-    a packed triple) -> (LlrResult, cnumerr histogram) in one library call."""
+    a packed triple) -> (LlrResult, cnumerr histogram) in one library call.
+    payload_nt: the payload length of a strand; the matrices have 2 * payload_nt rows."""
     mod, L = _lib()
     buf, offs, lens, q, iv, sidx, n = _native_inputs(index_vals, seqs, quals, strands)
     S = len(sidx)
+    nt = int(payload_nt)
     unit = math.log((1 - eps) / eps)  # decoder.py:297
-    llr = np.zeros((2 * PAYLOAD_NT, S), np.float64)
-    mask = np.zeros((2 * PAYLOAD_NT, S), np.uint8)
-    codes = np.zeros((2 * PAYLOAD_NT, S), np.int8)
+    llr = np.zeros((2 * max(nt, 1), S), np.float64)
+    mask = np.zeros((2 * max(nt, 1), S), np.uint8)
+    codes = np.zeros((2 * max(nt, 1), S), np.int8)
     kind = np.zeros(S, np.int32)
     stats = np.zeros(N_PLAN_STATS, np.int64)
     exact = C.c_int32(0)
     _native_check(mod, L.ldpc_dna_reads_llr(_p(buf), _p(offs), _p(lens), _p(q), n, None if iv is None else _p(iv),
-                                            _p(sidx), S, PAYLOAD_NT, 1 if align else 0, device, int(workspace_bytes),
+                                            _p(sidx), S, nt, 1 if align else 0, device, int(workspace_bytes),
                                             unit, _p(llr), _p(mask), _p(codes), C.byref(exact), _p(kind), _p(stats)))
     res = LlrResult(llr=llr, int_mask=mask, kind=kind, n_reads_valid=int(stats[0]), n_pairs=int(stats[1]),
                     n_aligned_strands=int(stats[2]), erased=np.nonzero(kind == KIND_NONE)[0],
@@ -639,25 +648,29 @@ def build_llr_native(index_vals, seqs, quals, eps: float = 0.02, align: bool = T
 
 def build_llr(index_vals: Sequence[int], seqs: Sequence[str], quals: Sequence[int], eps: float = 0.02,
               align_fn: Optional[AlignFn] = None, device: int = 0,
-              strands: Optional[np.ndarray] = None, native: bool = False) -> LlrResult:
+              strands: Optional[np.ndarray] = None, native: bool = False,
+              payload_nt: int = PAYLOAD_NT) -> LlrResult:
     """Reads (decoded index value, payload sequence, quality) -> LlrResult.
     `strands` defaults to strand_indices(); align_fn answers the MUSCLE call
     for ragged strands (required only if such strands have close pairs):
     "star" is the built-in aligner on `device`, a callable is asked per strand.
     native=True: the planner runs in the library too (ldpc_dna_reads_llr, one
     call; align_fn None or "star"; seqs may be a packed triple; t_align_s is
-    not measured and reads 0.0)."""
+    not measured and reads 0.0).  payload_nt: the payload length of a strand
+    in nucleotides; the matrices have 2 * payload_nt rows."""
     if native:
-        return build_llr_native(index_vals, seqs, quals, eps, _native_align(align_fn), device, strands)[0]
+        return build_llr_native(index_vals, seqs, quals, eps, _native_align(align_fn), device, strands,
+                                payload_nt=payload_nt)[0]
     mod, L = _lib()
-    plan = plan_llr(index_vals, seqs, quals, align_fn, device, strands)
+    plan = plan_llr(index_vals, seqs, quals, align_fn, device, strands, payload_nt=payload_nt)
+    nt = int(payload_nt)
     S = len(plan.kind)
     unit = math.log((1 - eps) / eps)  # decoder.py:297
-    llr = np.zeros((2 * PAYLOAD_NT, S), np.float64)
-    mask = np.zeros((2 * PAYLOAD_NT, S), np.uint8)
-    codes = np.zeros((2 * PAYLOAD_NT, S), np.int8)
+    llr = np.zeros((2 * nt, S), np.float64)
+    mask = np.zeros((2 * nt, S), np.uint8)
+    codes = np.zeros((2 * nt, S), np.int8)
     exact = C.c_int32(0)
-    mod._check(L.ldpc_dna_llr_codes(S, _p(plan.kind), _p(plan.row_ptr), _p(plan.rows), _p(plan.row_q), PAYLOAD_NT,
+    mod._check(L.ldpc_dna_llr_codes(S, _p(plan.kind), _p(plan.row_ptr), _p(plan.rows), _p(plan.row_q), nt,
                                     unit, _p(llr), _p(mask), _p(codes), C.byref(exact), device))
     return LlrResult(llr=llr, int_mask=mask, kind=plan.kind, n_reads_valid=plan.n_reads_valid,
                      n_pairs=plan.n_pairs, n_aligned_strands=plan.n_aligned_strands,

@@ -138,16 +138,20 @@ def _finish_trial(built, t_llr, codewords, eps, max_iter, decode_fn, faithful) -
 
 def trial_from_reads(reads, codewords: np.ndarray, eps: float = 0.02, max_iter: int = 200, align_fn=None,
                      decode_fn: Optional[DecodeFn] = None, faithful: bool = True, device: int = 0,
-                     native: bool = False) -> Dict:
+                     native: bool = False, strands=None, payload_nt: Optional[int] = None) -> Dict:
     """decoder.py:120-664 for one trial: reads (index values, payloads,
     qualities) -> LLRs on the GPU (dna_llr.build_llr) -> first and second
     decode.  align_fn: "star" (the built-in aligner, on the GPU) or a
     callable.  Adds the LLR stage's time and strand statistics to the result,
     the aligner's share among them (n_align_pairs, t_align_s).  native=True:
-    the planner runs in the library as well (build_llr(native=True))."""
+    the planner runs in the library as well (build_llr(native=True)).
+    strands, payload_nt: the strand index values and the payload length of
+    another code than the DNA file's (build_llr's defaults otherwise)."""
     import dna_llr
+    nt = dna_llr.PAYLOAD_NT if payload_nt is None else int(payload_nt)
     t0 = time.perf_counter()
-    built = dna_llr.build_llr(*reads, eps=eps, align_fn=align_fn, device=device, native=native)
+    built = dna_llr.build_llr(*reads, eps=eps, align_fn=align_fn, device=device, native=native, strands=strands,
+                              payload_nt=nt)
     t_llr = time.perf_counter() - t0
     return _finish_trial(built, t_llr, codewords, eps, max_iter, decode_fn, faithful)
 
@@ -172,20 +176,23 @@ def read_trial_files(directory: str, rs: int, trial: int):
 
 def trial_from_raw_reads(raw_reads, codewords: np.ndarray, eps: float = 0.02, max_iter: int = 200, align_fn=None,
                          decode_fn: Optional[DecodeFn] = None, faithful: bool = True, device: int = 0,
-                         host_index: bool = False, native: bool = False) -> Dict:
+                         host_index: bool = False, native: bool = False, strands=None,
+                         payload_nt: Optional[int] = None) -> Dict:
     """decoder.py:59-664 for one trial: raw reads (sequences, qualities) ->
     index decode on the GPU (dna_llr.split_reads; host_index=True: on the CPU)
     -> trial_from_reads.  Adds the index stage's time, the number of reads it
     dropped and the histogram of cnumerr.  native=True: the raw reads (a list
     of str or a packed (buf, offsets, lengths) triple) go straight to
     ldpc_dna_reads_llr -- index decode, planner and LLRs in one library call, so
-    t_index_s is 0.0 and its time is part of t_llr_s."""
+    t_index_s is 0.0 and its time is part of t_llr_s.  strands, payload_nt: as
+    in trial_from_reads."""
     import dna_llr
+    nt = dna_llr.PAYLOAD_NT if payload_nt is None else int(payload_nt)
     if native:
         seqs, quals = raw_reads
         t0 = time.perf_counter()
         built, hist = dna_llr.build_llr_native(None, seqs, quals, eps=eps, align=dna_llr._native_align(align_fn),
-                                               device=device)
+                                               device=device, strands=strands, payload_nt=nt)
         res = _finish_trial(built, time.perf_counter() - t0, codewords, eps, max_iter, decode_fn, faithful)
         res.update(t_index_s=0.0, n_reads_dropped=hist[-1], cnumerr_hist=hist)
         return res
@@ -193,7 +200,7 @@ def trial_from_raw_reads(raw_reads, codewords: np.ndarray, eps: float = 0.02, ma
     reads, hist = dna_llr.split_reads_counted(*raw_reads, device=device, host=host_index)
     t_index = time.perf_counter() - t0
     res = trial_from_reads(reads, codewords, eps=eps, max_iter=max_iter, align_fn=align_fn, decode_fn=decode_fn,
-                           faithful=faithful, device=device)
+                           faithful=faithful, device=device, strands=strands, payload_nt=nt)
     res.update(t_index_s=t_index, n_reads_dropped=hist[-1], cnumerr_hist=hist)
     return res
 
@@ -308,10 +315,15 @@ class ResidentTrial:
     second decode, n >= 2 at most n, -1 as many as fit in the tiles the failed
     rows occupy anyway.  Every run of the handle uses the setting; the result
     differs only in the counters second_decodes, second_rows, second_rows_used,
-    code_absmax and steps_per_decode, which every resident result carries."""
+    code_absmax and steps_per_decode, which every resident result carries.
+
+    The read calls (run_reads, run_raw, run_sim) take the payload length from
+    the handle, n_cw // 2 nucleotides, and the strand index values from
+    `strands`: N strictly increasing ints, dna_llr.strand_indices() by default
+    when N is the DNA file's 18432; a handle of another code needs them."""
 
     def __init__(self, graph, codewords: Optional[np.ndarray] = None, algo="bp", device: int = 0,
-                 n_cw: Optional[int] = None, schedule=None, speculate: int = 0):
+                 n_cw: Optional[int] = None, schedule=None, speculate: int = 0, strands=None):
         import ctypes as C
 
         import dna_llr
@@ -328,6 +340,16 @@ class ResidentTrial:
             n_cw = len(self.codewords)
         self.n_cw = int(2 * dna_llr.PAYLOAD_NT if n_cw is None else n_cw)
         self.N = graph.N
+        self.payload_nt = self.n_cw // 2  # an odd n_cw: the library's length check answers the read calls
+        self.strand_index = None  # the strand index values of the read calls
+        if strands is not None:
+            sidx = np.asarray(strands)
+            if sidx.ndim != 1 or len(sidx) != self.N or not np.issubdtype(sidx.dtype, np.integer) or \
+                    (np.diff(sidx.astype(np.int64)) <= 0).any():
+                raise ValueError(f"strands must be {self.N} strictly increasing int index values")
+            self.strand_index = sidx.astype(np.int64)
+        elif self.N == dna_llr.N_STRANDS:
+            self.strand_index = dna_llr.strand_indices()
         self.strands = None  # run_sim's, once set
         sch =ldpc_amd._schedule(schedule)
         err = C.c_int(0)
@@ -368,15 +390,21 @@ class ResidentTrial:
         res.update(self.counters())
         return res
 
+    def _strand_index(self) -> np.ndarray:
+        if self.strand_index is None:
+            raise ValueError(f"a handle of N = {self.N} strands needs their index values for the read calls: "
+                             "ResidentTrial(..., strands=...)")
+        return self.strand_index
+
     def _run_reads(self, index_vals, seqs, quals, eps, max_iter, align_fn, faithful, workspace_bytes):
         """ldpc_trial_run_reads -> the result dict, or None when the codes cannot carry the input."""
         import dna_llr
         mod, L = self._mod, self._L
-        buf, offs, lens, q, iv, sidx, n = dna_llr._native_inputs(index_vals, seqs, quals, None)
+        buf, offs, lens, q, iv, sidx, n = dna_llr._native_inputs(index_vals, seqs, quals, self._strand_index())
         out = _TrialOut(self.n_cw, self.N, n_strands=len(sidx))
         p = dna_llr._p
         rc = L.ldpc_trial_run_reads(self._h, p(buf), p(offs), p(lens), p(q), n, None if iv is None else p(iv), p(sidx),
-                                    len(sidx), dna_llr.PAYLOAD_NT, 1 if dna_llr._native_align(align_fn) else 0,
+                                    len(sidx), self.payload_nt, 1 if dna_llr._native_align(align_fn) else 0,
                                     int(workspace_bytes), float(eps), int(max_iter), int(bool(faithful)), out.ref())
         if rc == mod.LDPC_ERR_UNSUPPORTED and out.r.codes_exact == 0 and self.codewords is not None:
             return None
@@ -411,7 +439,8 @@ class ResidentTrial:
         res = self._run_reads(*reads, eps, max_iter, align_fn, faithful, workspace_bytes)
         if res is None:
             res = trial_from_reads(reads, self.codewords, eps=eps, max_iter=max_iter, align_fn=align_fn,
-                                   decode_fn=self._fallback_fn(), faithful=faithful, device=self.device, native=True)
+                                   decode_fn=self._fallback_fn(), faithful=faithful, device=self.device, native=True,
+                                   strands=self.strand_index, payload_nt=self.payload_nt)
             res["resident"] = False
         return res
 
@@ -430,7 +459,7 @@ class ResidentTrial:
         if res is None:
             res = trial_from_raw_reads(raw_reads, self.codewords, eps=eps, max_iter=max_iter, align_fn=align_fn,
                                        decode_fn=self._fallback_fn(), faithful=faithful, device=self.device,
-                                       native=True)
+                                       native=True, strands=self.strand_index, payload_nt=self.payload_nt)
             res["resident"] = False
             return res
         return self._raw_counts(res)
@@ -461,14 +490,17 @@ class ResidentTrial:
         import dna_llr
         import synth
         mod, L = self._mod, self._L
+        index = self._strand_index()
         if strands is not None:
             s = np.ascontiguousarray(strands, np.uint8)
             if self.strands is None or s.shape != self.strands.shape or (s != self.strands).any():
                 self.set_strands(s)
         elif self.strands is None and self.codewords is not None:
-            self.set_strands(synth.dna_strands(self.codewords))
+            self.set_strands(synth.dna_strands(self.codewords, index))
         t_sub, t_ins, t_del, q_val, q_lo = synth.sim_tables(sub, ins, dele, quality)
-        sidx = np.ascontiguousarray(dna_llr.strand_indices(), np.int32)
+        if index.size and (index.min() < -(1 << 31) or index.max() >= (1 << 31)):
+            raise ValueError("strand index values must fit int32")
+        sidx = np.ascontiguousarray(index, np.int32)
         out = _TrialOut(self.n_cw, self.N, n_strands=len(sidx))
         p = dna_llr._p
         rc = L.ldpc_trial_run_sim(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(r0), int(n_reads), t_sub, t_ins, t_del,

@@ -96,7 +96,7 @@ def test_handle_reuse_leaves_nothing_behind(small, gpu):
     re_decode accumulators, batch rows or flags would show."""
     G, cw, codes = small["irregular"]
     other = np.where((cw ^ synth.bsc_flips(0, 65, G.N, 9, 0.02).astype(np.uint8)) == 1, -1, 1).astype(np.int8)
-    T = P.ResidentTrial(G, cw)
+    T = P.ResidentTrial(G, cw, strands=np.arange(G.N))  # (index values: the read call below gets to the library)
     first = T.run_codes(codes, eps=EPS, max_iter=SMALL_ITERS)
     second = T.run_codes(other[:5], eps=EPS, max_iter=SMALL_ITERS, faithful=False)  # fewer rows than the handle holds
     third = T.run_codes(codes, eps=EPS, max_iter=SMALL_ITERS)
