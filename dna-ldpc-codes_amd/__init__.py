@@ -14,4 +14,4 @@ or simply put dna-ldpc-codes_amd/ on sys.path and ``import ldpc_amd``.
 """
 from . import ldpc_amd  # noqa: F401
 from . import synth  # noqa: F401
-from .ldpc_amd import Graph, Engine, Encoder, decode, decode_files, graph, device_count  # noqa: F401
+from .ldpc_amd import Graph, Engine, Encoder, ErrorRate, ber_curve, decode, decode_files, graph, device_count  # noqa: F401

@@ -1091,3 +1091,6 @@ int encode_launch(const EncoderDev& d, hipStream_t stream, const uint8_t* d_msg,
 }
 
 }  // namespace ldpc
+
+// --- the error-rate simulation (channel_sim.hpp, error_rate.hpp) ---
+#include "channel_sim_kernels.hpp"

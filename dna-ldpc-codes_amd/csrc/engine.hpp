@@ -204,6 +204,16 @@ struct Engine {
                 double p, double llr_mag);
     // the same channel as int8 codes: +1 for a received 0, -1 for a 1
     int gen_bsc_codes(int8_t* d_out, int64_t b0, int64_t B, const uint8_t* d_cw, int32_t n_cw, uint64_t seed, double p);
+    // the error-rate simulation's kernels (channel_sim_kernels.hpp, DESIGN.md
+    // sec. 8.11) on the engine's stream: message bits d_msg [B][K] of frames
+    // [b0, b0 + B); channel codes d_codes [B][N] of the codewords d_cw under
+    // the thresholds d_thr[254]; per-frame error records d_rec [B] (d_mask
+    // [N] the information positions, d_raw[256] chan::raw_table's bytes)
+    int sim_messages(uint8_t* d_msg, int32_t K, int64_t b0, int64_t B, uint64_t seed);
+    int channel_codes(const uint8_t* d_cw, int8_t* d_codes, int64_t b0, int64_t B, uint64_t seed, const uint64_t* d_thr);
+    int frame_errors(const uint8_t* d_hard, const uint8_t* d_cw, const int8_t* d_codes, const uint8_t* d_mask,
+                     const uint8_t* d_raw, const int32_t* d_iters, const uint8_t* d_valid, int64_t B,
+                     ldpc_ber_record* d_rec);
     // wait for the engine's stream, then LanePool::check_fault
     int sync();
     // ldpc_engine_profile / ldpc_engine_stats: wait for the stream and read the

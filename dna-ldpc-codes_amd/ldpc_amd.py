@@ -146,6 +146,9 @@ EXPORTS = [
     "ldpc_dna_sim_stride", "ldpc_dna_sim_reads_host", "ldpc_dna_sim_reads", "ldpc_trial_set_strands",
     "ldpc_trial_run_sim",
     "ldpc_dna_trial_host_spec", "ldpc_trial_set_speculation", "ldpc_trial_get_counters",
+    "ldpc_channel_codes_host", "ldpc_frame_errors_host", "ldpc_ber_run_host", "ldpc_ber_create", "ldpc_ber_free",
+    "ldpc_ber_set_params", "ldpc_ber_run_range", "ldpc_ber_run", "ldpc_ber_read", "ldpc_ber_frame_errors",
+    "ldpc_ber_profile", "ldpc_ber_stats",
 ]
 
 
@@ -762,3 +765,263 @@ class Encoder:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------
+# error-rate simulation (ldpc_ber_*, include/ldpc_amd.h "Error-rate
+# simulation"): encode -> channel -> decode -> count, the
+# whole loop on the GPU
+# ---------------------------------------------------------------------------
+class BerRecord(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("bit_err", "info_err", "raw_err", "erased", "iters", "valid")]
+
+
+BER_RECORD = np.dtype([(k, np.int32) for k, _ in BerRecord._fields_])
+BER_COUNTERS = ("frames", "bit_err", "info_err", "frame_err", "undetected", "detected", "raw_bit_err",
+                "raw_frame_err", "erased", "iter_sum")
+
+
+class BerResult(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in BER_COUNTERS] + [("iter_hist", C.c_void_p), ("n_hist", C.c_int32),
+                                                         ("reserved", C.c_int32)]
+
+
+BER_DECODE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                            C.c_void_p, C.c_void_p, C.c_void_p)
+_ber_bound = False
+
+
+def _ber_lib():
+    global _ber_bound
+    L = lib()
+    if not _ber_bound:
+        vp, i32, i64, u64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double
+        L.ldpc_channel_codes_host.argtypes = [vp, i32, i64, i64, u64, vp, vp]
+        L.ldpc_frame_errors_host.argtypes = [vp, vp, vp, i32, i64, vp, vp, i32, vp, vp, vp]
+        L.ldpc_ber_run_host.argtypes = [i32, vp, BER_DECODE_FN, vp, vp, vp, i32, u64, i64, i32, i64, i64, i64,
+                                        C.POINTER(BerResult)]
+        L.ldpc_ber_create.argtypes = [vp, vp, i32, i32, C.POINTER(Schedule), i64, C.POINTER(C.c_int)]
+        L.ldpc_ber_create.restype = vp
+        L.ldpc_ber_free.argtypes = [vp]
+        L.ldpc_ber_free.restype = None
+        L.ldpc_ber_set_params.argtypes = [vp, i32, dbl, i32, u64]
+        L.ldpc_ber_run_range.argtypes = [vp, vp, vp, i32, u64, i64, i64, i32, vp]
+        L.ldpc_ber_run.argtypes = [vp, vp, vp, i32, u64, i32, i64, i64, i64, C.POINTER(BerResult)]
+        L.ldpc_ber_read.argtypes = [vp, i64, vp, vp, vp]
+        L.ldpc_ber_frame_errors.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, i64, vp]
+        L.ldpc_ber_profile.argtypes = [vp, i32]
+        L.ldpc_ber_stats.argtypes = [vp, C.POINTER(KernelStats)]
+        _ber_bound = True
+    return L
+
+
+def _channel(channel):
+    """(thr, table[, table_kind]) -> contiguous arrays and the kind."""
+    thr = np.ascontiguousarray(channel[0], dtype=np.uint64)
+    table = np.ascontiguousarray(channel[1], dtype=np.float64)
+    if thr.shape != (254,) or table.shape != (256,):
+        raise ValueError("a channel is (thr[254], table[256]) (synth.awgn_channel / bsc_channel / bec_channel)")
+    return thr, table, int(channel[2]) if len(channel) > 2 else IN_LLR
+
+
+def _u8(a, shape, what):
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    if a.shape != shape:
+        raise ValueError(f"{what} must have shape {shape}")
+    return a
+
+
+def _ber_stop(frames, target_frame_errors, max_frames):
+    if (frames is None) == (target_frame_errors is None):
+        raise ValueError("give either frames or target_frame_errors")
+    if frames is not None:
+        if frames < 1:
+            raise ValueError("frames must be >= 1")
+        return int(frames), 0, 0
+    if max_frames is None:
+        raise ValueError("target_frame_errors needs max_frames")
+    return 0, int(target_frame_errors), int(max_frames)
+
+
+def _ber_dict(res: BerResult, hist: np.ndarray) -> dict:
+    d = {k: int(getattr(res, k)) for k in BER_COUNTERS}
+    d["iter_hist"] = hist.copy()
+    return d
+
+
+def channel_codes_host(cw, N: int, b0: int, B: int, seed: int, thr) -> np.ndarray:
+    """ldpc_channel_codes_host: codes [B][N] int8 of frames b0 .. b0 + B - 1;
+    cw [B][N] or None (the zero codeword)."""
+    thr = np.ascontiguousarray(thr, dtype=np.uint64)
+    if thr.shape != (254,):
+        raise ValueError("thr holds 254 thresholds")
+    c = None if cw is None else _u8(cw, (B, N), "cw")
+    out = np.zeros((max(B, 0), max(N, 0)), np.int8)
+    _check(_ber_lib().ldpc_channel_codes_host(_ptr(c), N, b0, B, seed, _ptr(thr), _ptr(out)))
+    return out
+
+
+def frame_errors_host(hard, cw, codes, info_mask, table, table_kind: int = IN_LLR, iters=None, valid=None):
+    """ldpc_frame_errors_host: the records (BER_RECORD) of hard / codes [B][N]."""
+    codes = np.ascontiguousarray(codes, dtype=np.int8)
+    B, N = codes.shape
+    hard = _u8(hard, (B, N), "hard")
+    cw = None if cw is None else _u8(cw, (B, N), "cw")
+    mask = None if info_mask is None else _u8(info_mask, (N,), "info_mask")
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    it = None if iters is None else np.ascontiguousarray(iters, dtype=np.int32)
+    v = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+    rec = np.zeros(B, BER_RECORD)
+    _check(_ber_lib().ldpc_frame_errors_host(_ptr(hard), _ptr(cw), _ptr(codes), N, B, _ptr(mask), _ptr(table),
+                                             table_kind, _ptr(it), _ptr(v), _ptr(rec)))
+    return rec
+
+
+def ber_run_host(N: int, enc: Optional["Encoder"], decode, channel, max_iter: int, seed: int, batch: int,
+                 frames=None, target_frame_errors=None, max_frames=None) -> dict:
+    """ldpc_ber_run_host: the error-rate loop on the CPU with the caller's
+    decoder, decode(codes [B][N] int8, table, table_kind, b0, max_iter) ->
+    (hard [B][N], iters [B], valid [B]).  enc None: the zero codeword."""
+    thr, table, kind = _channel(channel)
+    fr, tg, mx = _ber_stop(frames, target_frame_errors, max_frames)
+
+    def cb(user, p_codes, p_table, table_kind, b0, B, mi, p_hard, p_iters, p_valid):
+        try:
+            codes = np.ctypeslib.as_array(C.cast(p_codes, C.POINTER(C.c_int8)), (B, N))
+            tab = np.ctypeslib.as_array(C.cast(p_table, C.POINTER(C.c_double)), (256,))
+            h, it, v = decode(codes, tab, table_kind, b0, mi)
+            np.ctypeslib.as_array(C.cast(p_hard, C.POINTER(C.c_uint8)), (B, N))[:] = h
+            np.ctypeslib.as_array(C.cast(p_iters, C.POINTER(C.c_int32)), (B,))[:] = it
+            np.ctypeslib.as_array(C.cast(p_valid, C.POINTER(C.c_uint8)), (B,))[:] = v
+            return 0
+        except Exception:  # a Python error must not unwind through the C frames
+            import traceback
+            traceback.print_exc()
+            return LDPC_ERR_ARG
+
+    hist = np.zeros(max_iter + 1, np.int64)
+    res = BerResult(iter_hist=hist.ctypes.data, n_hist=hist.size)
+    _check(_ber_lib().ldpc_ber_run_host(N, enc._h if enc is not None else None, BER_DECODE_FN(cb), None, _ptr(thr),
+                                        _ptr(table), kind, seed, batch, max_iter, fr, tg, mx, C.byref(res)))
+    return _ber_dict(res, hist)
+
+
+class ErrorRate:
+    """Bit and frame error rates of a code and a decoder over a channel, the
+    whole loop on the GPU (ldpc_ber_*): per batch the messages, the systematic
+    encoder, the channel, the decoder and the error counter run on one
+    engine's stream, and 24 bytes per frame come back.
+
+        thr_table = synth.awgn_channel(ebno_db=4.0, rate=enc.K / enc.N)
+        er = ErrorRate(G, algo="bp", batch=4096)
+        r = er.run(thr_table, max_iter=50, seed=1, target_frame_errors=100, max_frames=10 ** 6)
+        fer, ber = r["frame_err"] / r["frames"], r["bit_err"] / (r["frames"] * G.N)
+
+    zero_codeword: no messages and no encoder, every frame is the zero word
+    (info_err then counts every position).  pool_tiles (a schedule keyword)
+    sets the engine's lane pool in tiles of 64 codewords; every other schedule
+    keyword is the Engine's.  The result of run does not depend on batch."""
+
+    def __init__(self, g: Graph, algo="bp", device: int = 0, batch: int = 1024, zero_codeword: bool = False,
+                 encoder: Optional[Encoder] = None, schedule=None, **sched_kw):
+        self.g, self.device, self.algo, self.batch = g, device, _algo(algo), int(batch)
+        self.enc = None if zero_codeword else (encoder if encoder is not None else g.encoder())
+        kw = dict(_schedule_kw(schedule))
+        kw.update({k: v for k, v in sched_kw.items() if v is not None})
+        sch = Schedule.make(**kw)
+        err = C.c_int(0)
+        self._h = _ber_lib().ldpc_ber_create(g.handle, self.enc._h if self.enc is not None else None, device,
+                                             self.algo, C.byref(sch), self.batch, C.byref(err))
+        if not self._h:
+            raise LdpcError(err.value, (lib().ldpc_last_error() or b"").decode(errors="replace"))
+
+    def set_params(self, msa_precision: int = 6, msa_step: float = 0.5, msa_offset: int = 0, tie_seed: int = 0):
+        """The quantised min-sum's parameters (Engine.set_params)."""
+        _check(lib().ldpc_ber_set_params(self._h, msa_precision, msa_step, msa_offset, tie_seed))
+
+    def run_range(self, channel, max_iter: int, seed: int, b0: int, B: int) -> np.ndarray:
+        """The records (BER_RECORD) of frames b0 .. b0 + B - 1."""
+        thr, table, kind = _channel(channel)
+        rec = np.zeros(B, BER_RECORD)
+        _check(lib().ldpc_ber_run_range(self._h, _ptr(thr), _ptr(table), kind, seed, b0, B, max_iter, _ptr(rec)))
+        return rec
+
+    def run(self, channel, max_iter: int, seed: int, frames=None, target_frame_errors=None, max_frames=None) -> dict:
+        """Frames 0, 1, ... until `frames` of them, or (target_frame_errors)
+        until the frame at which that many frame errors are reached, max_frames
+        at the latest.  A dict of the counters of ldpc_ber_result and
+        iter_hist[max_iter + 1]."""
+        thr, table, kind = _channel(channel)
+        fr, tg, mx = _ber_stop(frames, target_frame_errors, max_frames)
+        hist = np.zeros(max_iter + 1, np.int64)
+        res = BerResult(iter_hist=hist.ctypes.data, n_hist=hist.size)
+        _check(lib().ldpc_ber_run(self._h, _ptr(thr), _ptr(table), kind, seed, max_iter, fr, tg, mx, C.byref(res)))
+        return _ber_dict(res, hist)
+
+    def read(self, B: int):
+        """(cw, codes, hard) [B][N] of the last batch's first B rows (tests)."""
+        N = self.g.N
+        cw, codes, hard = np.zeros((B, N), np.uint8), np.zeros((B, N), np.int8), np.zeros((B, N), np.uint8)
+        _check(lib().ldpc_ber_read(self._h, B, _ptr(cw), _ptr(codes), _ptr(hard)))
+        return cw, codes, hard
+
+    def frame_errors(self, hard, cw, codes, table, table_kind: int = IN_LLR, iters=None, valid=None) -> np.ndarray:
+        """The error-counter kernel alone on host arrays (tests): as frame_errors_host
+        with the handle's information mask."""
+        codes = np.ascontiguousarray(codes, dtype=np.int8)
+        B, N = codes.shape
+        if N != self.g.N:
+            raise ValueError("codes must be [B][N]")
+        hard = _u8(hard, (B, N), "hard")
+        cw = None if cw is None else _u8(cw, (B, N), "cw")
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        it = None if iters is None else np.ascontiguousarray(iters, dtype=np.int32)
+        v = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+        rec = np.zeros(B, BER_RECORD)
+        _check(lib().ldpc_ber_frame_errors(self._h, _ptr(hard), _ptr(cw), _ptr(codes), _ptr(table), table_kind,
+                                           _ptr(it), _ptr(v), B, _ptr(rec)))
+        return rec
+
+    def profile(self, stride: int):
+        _check(lib().ldpc_ber_profile(self._h, int(stride)))
+
+    def stats(self) -> dict:
+        s = KernelStats()
+        _check(lib().ldpc_ber_stats(self._h, C.byref(s)))
+        return {k: {"launches": int(s.launches[i]), "sampled": int(s.sampled[i]), "ms": float(s.ms[i])}
+                for i, k in enumerate(KCLASS)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().ldpc_ber_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ber_curve(g: Graph, ebno_dbs, max_iter: int = 50, seed: int = 0, algo="bp", step: float = 1 / 16,
+              frames=None, target_frame_errors=None, max_frames=None, **kw) -> list:
+    """One ErrorRate.run result per Eb/N0 point (dB) over the quantised AWGN
+    channel of synth.awgn_channel at the code's rate K / N; each dict also
+    carries ebno_db, ber and fer.  kw: ErrorRate's keywords."""
+    try:
+        from . import synth
+    except ImportError:  # loaded as a top-level module
+        import synth
+    er = ErrorRate(g, algo=algo, **kw)
+    try:
+        rate = (er.enc.K if er.enc is not None else g.N - g.M) / g.N
+        out = []
+        for e in ebno_dbs:
+            r = er.run(synth.awgn_channel(float(e), rate, step), max_iter, seed, frames=frames,
+                       target_frame_errors=target_frame_errors, max_frames=max_frames)
+            r.update(ebno_db=float(e), fer=r["frame_err"] / max(r["frames"], 1),
+                     ber=r["bit_err"] / max(r["frames"] * g.N, 1))
+            out.append(r)
+        return out
+    finally:
+        er.close()

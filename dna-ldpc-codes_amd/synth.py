@@ -131,6 +131,85 @@ def random_codewords(enc, b0: int, B: int, seed: int, device=None) -> np.ndarray
     return enc.encode_host(m) if device is None else enc.encode(m, device=device)
 
 
+# --- the transmission channel of the error-rate simulation --
+# A symmetric memoryless channel with at most 255 outputs, as data: thr[254]
+# uint64 thresholds (non-decreasing, <= 2^53) and the 256-entry code table of
+# decode_codes.  csrc/channel_sim.hpp is the definition; channel_codes below is
+# its numpy replica, integer compares only.
+CHANNEL_STREAM = 0x4348414E4E454C31  # "CHANNEL1": keeps the channel's draws apart from the messages'
+CHANNEL_THR = 254
+
+
+def std_dev(ebno_db: float, rate: float) -> float:
+    """getStd_dev (channel.cpp:9-16), in its operation order."""
+    enl = math.pow(10.0, ebno_db * 0.1)
+    return 1 / math.sqrt(2 * rate * enl)
+
+
+def _phi(x: float) -> float:
+    return 0.5 * math.erfc(-x / math.sqrt(2.0))
+
+
+def _thr(p) -> np.ndarray:
+    """Cumulative probabilities -> thresholds: floor(2^53 p), made monotone, capped at 2^53."""
+    t = [min(SIM_ONE, max(0, int(math.floor(SIM_ONE * float(v))))) for v in p]
+    return np.maximum.accumulate(np.array(t, np.uint64))
+
+
+def awgn_channel(ebno_db: float, rate: float, step: float = 1 / 16):
+    """(thr, llr_table): BPSK over AWGN at Eb/N0 `ebno_db` for a code of rate
+    `rate`, y = +-1 + n quantised to k = clamp(round(y / step), +-127).
+    thr[i] = floor(2^53 Phi(((i - 126.5) step - 1) / sigma)), table[k + 128] =
+    2 k step / sigma^2 (channel.cpp:32)."""
+    s = std_dev(ebno_db, rate)
+    thr = _thr(_phi(((i - 126.5) * step - 1) / s) for i in range(CHANNEL_THR))
+    k = np.arange(-128, 128, dtype=np.float64)
+    return thr, np.ascontiguousarray(2.0 * (k * step) / (s * s))
+
+
+def bsc_channel(p: float):
+    """(thr, llr_table): codes +-1, a flip with probability p, LLR
+    +-ln((1 - p) / p) (channel.cpp:71-84)."""
+    thr = _thr([0.0] * 126 + [p, p] + [1.0] * 126)
+    table = np.zeros(256)
+    table[129], table[127] = math.log((1 - p) / p), math.log(p / (1 - p))
+    return thr, table
+
+
+def bec_channel(eps: float, mag: float = 30.0):
+    """(thr, llr_table): code 0 (LLR 0) with probability eps, else +-1 with LLR +-mag."""
+    thr = _thr([0.0] * 127 + [eps] + [1.0] * 126)
+    table = np.zeros(256)
+    table[129], table[127] = mag, -mag
+    return thr, table
+
+
+def channel_probs(thr: np.ndarray) -> np.ndarray:
+    """p[k + 127], k = -127 .. 127: the probability of code k on a transmitted 0, read from thr itself."""
+    t = np.concatenate([[0], np.asarray(thr, np.uint64).astype(np.float64), [float(SIM_ONE)]])
+    return np.diff(t) / float(SIM_ONE)
+
+
+def channel_codes(cw: np.ndarray, b0: int, B: int, seed: int, thr: np.ndarray) -> np.ndarray:
+    """[B][N] int8: the codes of frames b0 .. b0 + B - 1 whose transmitted
+    words are cw [B][N] (csrc/channel_sim.hpp):
+    u = splitmix64(((b << 24) | j) ^ splitmix64(seed ^ CHANNEL_STREAM)) >> 11,
+    k0 = -127 + #{i : u >= thr[i]}, code = -k0 where the bit is 1, else k0."""
+    cw = np.asarray(cw)
+    thr = np.asarray(thr, np.uint64)
+    if cw.shape[0] != B or thr.shape != (CHANNEL_THR,):
+        raise ValueError("cw must be [B][N] and thr hold 254 thresholds")
+    N = cw.shape[1]
+    if not 0 < N < (1 << 24) or b0 < 0 or b0 + B > (1 << 40):
+        raise ValueError("N must be below 2^24 and the frames below 2^40")
+    key = _splitmix64(np.array([(seed ^ CHANNEL_STREAM) & 0xFFFFFFFFFFFFFFFF], np.uint64))[0]
+    b = np.arange(b0, b0 + B, dtype=np.uint64)[:, None]
+    j = np.arange(N, dtype=np.uint64)[None, :]
+    u = _splitmix64(((b << np.uint64(24)) | j) ^ key) >> np.uint64(11)
+    k0 = np.searchsorted(thr, u.ravel(), side="right").reshape(B, N).astype(np.int64) - 127
+    return np.ascontiguousarray(np.where((cw & 1) != 0, -k0, k0).astype(np.int8))
+
+
 # --- sequenced reads for the LLR-construction stage -----
 DNA_FIXTURES = os.path.join(GOLDEN, "dna_fixtures.npz")
 _BASES = np.frombuffer(b"ACGT", np.uint8)

@@ -783,6 +783,122 @@ int ldpc_write_soft_files(const char *dir, int32_t rs, const double *llr, const 
 int ldpc_py_float_repr(double v, char *out, int32_t cap);
 
 /* ------------------------------------------------------------------------ */
+/* Error-rate simulation (the reference's                */
+/* Run_Simulation / Check_End loop, DNA_main.cpp:756-914, and channel.cpp)    */
+/* ------------------------------------------------------------------------ */
+/* The channel: symmetric, memoryless, at most 255 outputs, given as data.
+ * thr[254]: u64 thresholds, non-decreasing, each <= 2^53.  For frame b < 2^40
+ * and bit j < 2^24 (so N < 2^24):
+ *   u    = splitmix64(((b << 24) | j) ^ splitmix64(seed ^ 0x4348414e4e454c31)) >> 11
+ *   k0   = -127 + #{i : u >= thr[i]}
+ *   code = cw[b][j] ? -k0 : k0                    (int8, -127 .. 127)
+ * and the channel value of a code is table[code + 128], as for
+ * ldpc_decode_codes.  Integer compares only: the host form, the kernel and a
+ * numpy replica give the same bytes, and a range of frames gives the same rows
+ * however it is split.  The message of frame b is bit k = the low bit of
+ * splitmix64(((b << 24) | k) ^ splitmix64(seed)), encoded systematically.
+ *
+ * ldpc_channel_codes_host: codes [B][N] of frames [b0, b0 + B) on one CPU
+ * thread; cw [B][N] u8 (bit 0 is used) or NULL: the zero codeword.  A NULL or
+ * non-monotone thr, a threshold above 2^53, N outside 1 .. 2^24 - 1, negative
+ * b0 / B and frames past 2^40 are LDPC_ERR_ARG, before anything is written. */
+int ldpc_channel_codes_host(const uint8_t *cw, int32_t N, int64_t b0, int64_t B, uint64_t seed, const uint64_t *thr,
+                            int8_t *codes);
+
+/* One frame's record.  bit_err: positions with hard != cw, over all N;
+ * info_err: the same over the information positions; raw_err: positions where
+ * the channel value read hard differs from cw, by the reference's rule
+ * (DNA_main.cpp:1711-1748: an LLR >= 0, or a likelihood ratio >= 1, reads as
+ * 0, anything else -- a NaN too -- as 1), over all N; erased: positions with
+ * code == 0; iters / valid: the decoder's iteration count and *bIsCodeword. */
+typedef struct ldpc_ber_record {
+    int32_t bit_err, info_err, raw_err, erased, iters, valid;
+} ldpc_ber_record;
+
+/* The error counter on one CPU thread: records [B] from hard / codes [B][N],
+ * cw [B][N] or NULL (zeros), info_mask [N] (1 at an information position) or
+ * NULL (every position), the code table, and iters / valid [B] (NULL: 0). */
+int ldpc_frame_errors_host(const uint8_t *hard, const uint8_t *cw, const int8_t *codes, int32_t N, int64_t B,
+                           const uint8_t *info_mask, const double *table, int32_t table_kind, const int32_t *iters,
+                           const uint8_t *valid, ldpc_ber_record *records);
+
+/* The totals of a run.  frame_err: frames with bit_err > 0; undetected: those
+ * among them the decoder called a codeword (DNA_main.cpp:871-874); detected:
+ * frames with valid == 0; raw_frame_err: frames with raw_err > 0; iter_hist
+ * (caller-owned, may be NULL; n_hist >= max_iter + 1 bins, else LDPC_ERR_ARG):
+ * frames per iteration count.  A run resets every counter. */
+typedef struct ldpc_ber_result {
+    int64_t frames, bit_err, info_err, frame_err, undetected, detected;
+    int64_t raw_bit_err, raw_frame_err, erased, iter_sum;
+    int64_t *iter_hist;
+    int32_t n_hist, reserved;
+} ldpc_ber_result;
+
+/* The stop rule of every run (Check_End, DNA_main.cpp:756-795).  Frames are
+ * taken in index order from 0.  frames > 0: exactly that many.  frames == 0:
+ * the run ends after the frame at which frame_err reaches target_frame_err
+ * (>= 1), and after max_frames (>= 1) frames at the latest.  Batches run
+ * whole; records past the cut are dropped, so the result does not depend on
+ * the batch size.
+ *
+ * ldpc_ber_run_host: the loop on host buffers with the caller's decoder (the
+ * library has no CPU decoder): decode frames [b0, b0 + B), codes [B][N] under
+ * table, into hard [B][N], iters [B] (0 .. max_iter) and valid [B]; a nonzero
+ * return ends the run with it.  enc: the messages above through
+ * ldpc_encode_host, info_err over its info_pos; NULL: the zero codeword, and
+ * info_err counts every position. */
+typedef int (*ldpc_ber_decode_fn)(void *user, const int8_t *codes, const double *table, int32_t table_kind,
+                                  int64_t b0, int64_t B, int32_t max_iter, uint8_t *hard, int32_t *iters,
+                                  uint8_t *valid);
+int ldpc_ber_run_host(int32_t N, const ldpc_encoder *enc, ldpc_ber_decode_fn decode, void *user, const uint64_t *thr,
+                      const double *table, int32_t table_kind, uint64_t seed, int64_t batch, int32_t max_iter,
+                      int64_t frames, int64_t target_frame_err, int64_t max_frames, ldpc_ber_result *result);
+
+/* The device handle: one engine (any algo; its lane pool sized as
+ * ldpc_decode_codes sizes it for `batch` codewords), the buffers of one batch
+ * (messages, codewords, codes, hard bits, iters, valid, records) on `device`
+ * and pinned host records, created once.  A batch never leaves the device:
+ * message kernel -> ldpc_encoder_encode_device -> channel kernel ->
+ * ldpc_engine_decode_codes -> error counter, all on the engine's stream; the
+ * host reads 24 bytes per frame.  enc as for ldpc_ber_run_host.  The lane
+ * pool is schedule->pool_tiles tiles of 64 codewords when that is set.  The
+ * graph and the encoder must outlive the handle; a handle serves one thread
+ * at a time.  1 <= batch <= 2^20.  Argument errors are reported before any
+ * device call; without a GPU good arguments give LDPC_ERR_DEVICE. */
+typedef struct ldpc_ber ldpc_ber;
+ldpc_ber *ldpc_ber_create(const ldpc_graph *g, const ldpc_encoder *enc, int32_t device, int32_t algo,
+                          const ldpc_schedule *schedule, int64_t batch, int *err);
+void ldpc_ber_free(ldpc_ber *h);
+
+/* ldpc_engine_set_params of the handle's engine (LDPC_ALGO_QMSA); the tie
+ * hash of frame b keys on b itself. */
+int ldpc_ber_set_params(ldpc_ber *h, int32_t msa_precision, double msa_step, int32_t msa_offset, uint64_t tie_seed);
+
+/* Frames [b0, b0 + B) in batches: their records to records_out [B] (host).
+ * What a caller that shards frames over devices needs. */
+int ldpc_ber_run_range(ldpc_ber *h, const uint64_t *thr, const double *table, int32_t table_kind, uint64_t seed,
+                       int64_t b0, int64_t B, int32_t max_iter, ldpc_ber_record *records_out);
+
+/* The loop with the stop rule above, batches of the handle's size. */
+int ldpc_ber_run(ldpc_ber *h, const uint64_t *thr, const double *table, int32_t table_kind, uint64_t seed,
+                 int32_t max_iter, int64_t frames, int64_t target_frame_err, int64_t max_frames,
+                 ldpc_ber_result *result);
+
+/* Tests and tools.  ldpc_ber_read: rows [0, B) of the handle's last batch,
+ * B <= batch, to host cw / hard [B][N] u8 and codes [B][N] int8 (any may be
+ * NULL).  ldpc_ber_frame_errors: the error-counter kernel alone on host
+ * arrays (as ldpc_frame_errors_host, the handle's information mask; cw /
+ * iters / valid may be NULL: zeros), B <= batch.  ldpc_ber_profile /
+ * ldpc_ber_stats: ldpc_engine_profile / ldpc_engine_stats of the handle's
+ * engine; the three kernels of this section are launches of class "other". */
+int ldpc_ber_read(ldpc_ber *h, int64_t B, uint8_t *cw, int8_t *codes, uint8_t *hard);
+int ldpc_ber_frame_errors(ldpc_ber *h, const uint8_t *hard, const uint8_t *cw, const int8_t *codes,
+                          const double *table, int32_t table_kind, const int32_t *iters, const uint8_t *valid,
+                          int64_t B, ldpc_ber_record *records);
+int ldpc_ber_profile(ldpc_ber *h, int32_t stride);
+int ldpc_ber_stats(ldpc_ber *h, ldpc_kernel_stats *out);
+
+/* ------------------------------------------------------------------------ */
 /* misc                                                                      */
 /* ------------------------------------------------------------------------ */
 const char *ldpc_last_error(void); /* thread-local message for the last failing call */
