@@ -1036,7 +1036,10 @@ int Engine::expand_lr(const int8_t* d_code, const double* d_table, double* d_out
     if (n <= 0) return LDPC_OK;
     LDPC_HIP(hipSetDevice(device));
     const int64_t blocks = std::min<int64_t>(4096, (n / 8 + 255) / 256 + 1);
-    return sampler.launch(K_UNCOUNTED, s, dev::k_lr_table, dim3((unsigned)blocks), dim3(256), d_code, d_table, d_out, n);
+    // the caller's codes may sit at any byte (ldpc_engine_decode_codes states no alignment): 8-byte loads only when aligned
+    const int vec8 = reinterpret_cast<uintptr_t>(d_code) % 8 == 0 ? 1 : 0;
+    return sampler.launch(K_UNCOUNTED, s, dev::k_lr_table, dim3((unsigned)blocks), dim3(256), d_code, d_table, d_out, n,
+                          vec8);
 }
 
 int Engine::pack_bits(const uint8_t* d_in, uint8_t* d_out, int64_t nbytes)

@@ -2388,9 +2388,9 @@ __global__ __launch_bounds__(256) void k_pack_bits(const uint64_t* __restrict__ 
 }
 
 __global__ __launch_bounds__(256) void k_lr_table(const int8_t* __restrict__ code, const double* __restrict__ table,
-                                                  double* __restrict__ out, int64_t n)
+                                                  double* __restrict__ out, int64_t n, int vec8)
 {
-    const int64_t n8 = n / 8;
+    const int64_t n8 = vec8 ? n / 8 : 0;  // vec8: `code` is 8-byte aligned (the host looks at the pointer)
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n8; q += (int64_t)gridDim.x * blockDim.x) {
         const uint64_t c = reinterpret_cast<const uint64_t*>(code)[q];
 #pragma unroll

@@ -35,6 +35,11 @@ def edges(name):
         return refdec_cases.irregular_edges()
     if name == "q64":  # N = 4608: the error counter's block-per-frame shape
         return _regular_graph(np.random.default_rng(64), 64)
+    if name in ("n2048", "n2049"):  # the error counter's last wave-per-frame size; the first block-per-frame one, N % 8 != 0
+        N = int(name[1:])
+        rows = [j % 64 for j in range(N)] + [(j + 1) % 64 for j in range(0, N, 2)]
+        cols = list(range(N)) + list(range(0, N, 2))
+        return 64, N, rows, cols
     if name == "n13":  # N = 13: shorter than two words, not a multiple of 8
         rows = [j % 4 for j in range(13)] + [(j + 1) % 4 for j in range(0, 13, 2)]
         cols = list(range(13)) + list(range(0, 13, 2))
@@ -149,6 +154,7 @@ def planted(rng, B, N, mask):
     codes = rng.integers(-127, 128, (B, N)).astype(np.int8)
     codes[rng.random((B, N)) < 0.05] = 0
     codes[3, 0], codes[3, N - 1] = 3, -5  # nan_table's NaN entries
+    codes[4, N // 2] = -128  # table index 0 (the channel kernel never emits it; a caller's codes may)
     hard[0] = cw[0]
     hard[1] = cw[1] ^ (mask == 0)
     hard[2] = cw[2] ^ 1

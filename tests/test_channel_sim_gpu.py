@@ -108,8 +108,11 @@ def test_zero_codeword_skips_messages_and_encoder(gpu, code, handle):
 # ---------------------------------------------------------------------------
 # k_frame_errors: one wave per frame up to N = 2048, one block per frame above
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("name,N", [("n13", 13), ("r96", 96), ("irr", 130), ("r288", 288), ("q64", 4608)])
+@pytest.mark.parametrize("name,N", [("n13", 13), ("r96", 96), ("irr", 130), ("r288", 288), ("q64", 4608),
+                                    ("n2048", 2048), ("n2049", 2049)])
 def test_frame_errors_kernel_equals_host_form(gpu, code, handle, name, N):
+    """N = 2048 is the last wave-per-frame size; 2049 the smallest block-per-
+    frame one, and not a multiple of 8 (q64's 4608 is)."""
     c = code(name)
     assert c.N == N
     rng = np.random.default_rng(2000 + N)
@@ -156,6 +159,16 @@ def test_run_range_far_frames(gpu, code, handle):
     ch = _channel(c.rate)
     want = cc.reference_records(c.og, c.enc, ch, "bp", SEED, FAR, 100)
     assert np.array_equal(handle("r96", pool_tiles=1).run_range(ch, cc.MAX_ITER, SEED, FAR, 100), want)
+
+
+def test_run_range_batch_above_1024_takes_the_engines_own_pool(gpu, code, handle):
+    """ldpc_ber_create sizes the lane pool for `batch` codewords only up to
+    1024; above that the engine chooses its own: 1100 frames in one batch."""
+    c = code("r96")
+    ch = _channel(c.rate)
+    want = cc.reference_records(c.og, c.enc, ch, "bp", SEED, 0, 1100)
+    assert (want["bit_err"] > 0).any() and (want["bit_err"] == 0).any() and len(set(want["iters"])) > 3
+    assert np.array_equal(handle("r96", batch=1100).run_range(ch, cc.MAX_ITER, SEED, 0, 1100), want)
 
 
 def test_run_range_quantised_min_sum(gpu, code, handle):
