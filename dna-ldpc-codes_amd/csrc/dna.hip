@@ -2,7 +2,9 @@
 // read candidates -> the 272 x 18432 LLR matrix the first decode consumes,
 // plus the pairwise edit distances that pick which ragged candidates go to
 // the aligner, and the aligner itself (the centre-star alignment of
-// star_align.hpp, DESIGN.md sec. 8.6: k_star_align_pairs).
+// star_align.hpp, DESIGN.md sec. 8.6: k_star_align_pairs; star_align_device
+// keeps the uploads, the centre search, the pass loop and the downloads, the
+// layout of the pairs is star_align.hpp's host code).
 //
 // Reference: ex_decoder/decoder.py:142-519 (the strand loop; count rule
 // :266-320 and :442-497), def_func.py:10-26 (edit_dist), :97-117
@@ -38,6 +40,11 @@
 // included last.  The step before all of it, strands -> raw reads through a
 // counter-hashed substitution / insertion / deletion channel (dna_sim.hpp,
 // DESIGN.md sec. 8.9): dna_sim_kernels.hpp.
+//
+// Host code of this file and its three fragments: every kernel goes through
+// launch() and every blocking copy down through download() (hip_own.hpp), the
+// extent check of ragged reads is ragged_reads.hpp's, and dna_guard is the one
+// bad_alloc guard of the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,6 +59,7 @@
 #include "dna_sim.hpp"
 #include "dna_trial.hpp"
 #include "host_decode.hpp"  // ldpc_graph
+#include "ragged_reads.hpp"
 #include "rs_index.hpp"
 #include "star_align.hpp"
 
@@ -349,10 +357,8 @@ int launch_edit_distance(const uint8_t* d_seqs, const int64_t* d_off, const int3
                          const int32_t* d_pb, int64_t n_pairs, int32_t max_len, int32_t* d_dist)
 {
     const size_t lds = (sizeof(uint16_t) * (size_t)(max_len + 1) + (size_t)max_len) * 64;
-    hipLaunchKernelGGL(k_edit_distance, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), lds, 0, d_seqs, d_off, d_len,
-                       d_pa, d_pb, n_pairs, max_len, d_dist);
-    LDPC_HIP(hipGetLastError());
-    return LDPC_OK;
+    return launch(k_edit_distance, dim3((unsigned)((n_pairs + 63) / 64)), dim3(64), lds, nullptr, d_seqs, d_off, d_len,
+                  d_pa, d_pb, n_pairs, max_len, d_dist);
 }
 
 // k_dna_llr on a device-resident plan; d_mask, d_codes / d_overflow may be null.
@@ -361,10 +367,20 @@ int launch_dna_llr(const int32_t* d_kind, const int64_t* d_row_ptr, const uint8_
                    int8_t* d_codes, int32_t* d_overflow)
 {
     dim3 grid((unsigned)((n_strands + 255) / 256), (unsigned)payload_nt);
-    hipLaunchKernelGGL(k_dna_llr, grid, dim3(256), 0, 0, d_kind, d_row_ptr, d_rows, d_row_q, n_strands, payload_nt,
-                       llr_unit, d_llr, d_mask, d_codes, d_overflow);
-    LDPC_HIP(hipGetLastError());
-    return LDPC_OK;
+    return launch(k_dna_llr, grid, dim3(256), 0, nullptr, d_kind, d_row_ptr, d_rows, d_row_q, n_strands, payload_nt,
+                  llr_unit, d_llr, d_mask, d_codes, d_overflow);
+}
+
+// The one guard of the entry points that allocate host memory.
+template <class F>
+int dna_guard(const char* who, F&& f)
+{
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        set_error(std::string(who) + ": out of host memory");
+        return LDPC_ERR_DEVICE;
+    }
 }
 
 }  // namespace
@@ -387,13 +403,11 @@ int ldpc_dna_edit_distance(const uint8_t* seqs, const int64_t* offsets, const in
     if (n_pairs == 0) return LDPC_OK;
     int64_t total = 0;
     int32_t max_len = 0;
-    for (int64_t i = 0; i < n_seqs; i++) {
-        if (lengths[i] < 0 || offsets[i] < 0 || offsets[i] > INT64_MAX - lengths[i]) {
-            set_error("ldpc_dna_edit_distance: negative or overflowing length/offset");
-            return LDPC_ERR_ARG;
-        }
-        total = std::max<int64_t>(total, offsets[i] + lengths[i]);
-        max_len = std::max(max_len, lengths[i]);
+    // (the pair and length checks come before the null check here, and empty reads count into total)
+    const std::string err = ragged::extent(offsets, lengths, n_seqs, &total, true, &max_len);
+    if (!err.empty()) {
+        set_error("ldpc_dna_edit_distance: " + err);
+        return LDPC_ERR_ARG;
     }
     for (int64_t p = 0; p < n_pairs; p++) {
         if (pair_a[p] < 0 || pair_a[p] >= n_seqs || pair_b[p] < 0 || pair_b[p] >= n_seqs) {
@@ -414,17 +428,12 @@ int ldpc_dna_edit_distance(const uint8_t* seqs, const int64_t* offsets, const in
     dev_ptr<int64_t> doff;
     dev_ptr<int32_t> dlen, da, db, dd;
     int rc;
-    if ((rc = upload(ds, seqs, (size_t)total))) return rc;
-    if ((rc = upload(doff, offsets, (size_t)n_seqs))) return rc;
-    if ((rc = upload(dlen, lengths, (size_t)n_seqs))) return rc;
-    if ((rc = upload(da, pair_a, (size_t)n_pairs))) return rc;
-    if ((rc = upload(db, pair_b, (size_t)n_pairs))) return rc;
-    if ((rc = dev_alloc(dd, (size_t)n_pairs))) return rc;
-    if ((rc = launch_edit_distance(ds.get(), doff.get(), dlen.get(), da.get(),
-                                   db.get(), n_pairs, max_len, dd.get())))
+    if ((rc = upload(ds, seqs, (size_t)total)) || (rc = upload(doff, offsets, (size_t)n_seqs)) ||
+        (rc = upload(dlen, lengths, (size_t)n_seqs)) || (rc = upload(da, pair_a, (size_t)n_pairs)) ||
+        (rc = upload(db, pair_b, (size_t)n_pairs)) || (rc = dev_alloc(dd, (size_t)n_pairs)) ||
+        (rc = launch_edit_distance(ds.get(), doff.get(), dlen.get(), da.get(), db.get(), n_pairs, max_len, dd.get())))
         return rc;
-    LDPC_HIP(hipMemcpy(dist, dd.get(), sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost));
-    return LDPC_OK;
+    return download(dist, dd.get(), (size_t)n_pairs);
 }
 
 int ldpc_dna_index_encode(const int32_t* index, int64_t n, uint8_t* prefix)
@@ -456,15 +465,9 @@ static int index_decode_args(const char* who, const uint8_t* seqs, const int64_t
         set_error(std::string(who) + ": bad arguments");
         return LDPC_ERR_ARG;
     }
-    for (int64_t i = 0; i < n; i++) {
-        if (lengths[i] < 0 || offsets[i] < 0 || offsets[i] > INT64_MAX - lengths[i]) {
-            set_error(std::string(who) + ": negative or overflowing length/offset");
-            return LDPC_ERR_ARG;
-        }
-        if (lengths[i] > 0) *total = std::max<int64_t>(*total, offsets[i] + lengths[i]);
-    }
-    if (*total > 0 && !seqs) {
-        set_error(std::string(who) + ": null sequences");
+    const std::string err = ldpc::ragged::check(seqs, offsets, lengths, n, total);
+    if (!err.empty()) {
+        set_error(std::string(who) + ": " + err);
         return LDPC_ERR_ARG;
     }
     return LDPC_OK;
@@ -498,17 +501,13 @@ int ldpc_dna_index_decode(const uint8_t* seqs, const int64_t* offsets, const int
     dev_ptr<int64_t> doff;
     dev_ptr<int32_t> dlen, di, dc;
     int rc;
-    if ((rc = upload(ds, seqs, (size_t)total))) return rc;
-    if ((rc = upload(doff, offsets, (size_t)n))) return rc;
-    if ((rc = upload(dlen, lengths, (size_t)n))) return rc;
-    if ((rc = dev_alloc(di, (size_t)n))) return rc;
-    if ((rc = dev_alloc(dc, (size_t)n))) return rc;
-    hipLaunchKernelGGL(k_rs_index_decode, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ds.get(),
-                       doff.get(), dlen.get(), n, di.get(), dc.get());
-    LDPC_HIP(hipGetLastError());
-    LDPC_HIP(hipMemcpy(index, di.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-    LDPC_HIP(hipMemcpy(cnumerr, dc.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-    return LDPC_OK;
+    if ((rc = upload(ds, seqs, (size_t)total)) || (rc = upload(doff, offsets, (size_t)n)) ||
+        (rc = upload(dlen, lengths, (size_t)n)) || (rc = dev_alloc(di, (size_t)n)) || (rc = dev_alloc(dc, (size_t)n)) ||
+        (rc = launch(k_rs_index_decode, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, ds.get(), doff.get(),
+                     dlen.get(), n, di.get(), dc.get())) ||
+        (rc = download(index, di.get(), (size_t)n)))
+        return rc;
+    return download(cnumerr, dc.get(), (size_t)n);
 }
 
 // Shared argument check of the two strand writers.
@@ -566,14 +565,12 @@ int ldpc_dna_strands(const uint8_t* codewords, int32_t n_cw, int64_t N, const in
     dev_ptr<uint8_t> dcw, dout;
     dev_ptr<int32_t> di;
     int rc;
-    if ((rc = upload(dcw, codewords, (size_t)n_cw * (size_t)N))) return rc;
-    if ((rc = upload(di, index, (size_t)N))) return rc;
-    if ((rc = dev_alloc(dout, (size_t)N * (size_t)L))) return rc;
-    hipLaunchKernelGGL(k_strands_write, dim3((unsigned)((N + kStrTile - 1) / kStrTile), (unsigned)chunks), dim3(256),
-                       0, 0, dcw.get(), di.get(), n_cw, N, dout.get());
-    LDPC_HIP(hipGetLastError());
-    LDPC_HIP(hipMemcpy(out, dout.get(), (size_t)N * (size_t)L, hipMemcpyDeviceToHost));
-    return LDPC_OK;
+    if ((rc = upload(dcw, codewords, (size_t)n_cw * (size_t)N)) || (rc = upload(di, index, (size_t)N)) ||
+        (rc = dev_alloc(dout, (size_t)N * (size_t)L)) ||
+        (rc = launch(k_strands_write, dim3((unsigned)((N + kStrTile - 1) / kStrTile), (unsigned)chunks), dim3(256), 0,
+                     nullptr, dcw.get(), di.get(), n_cw, N, dout.get())))
+        return rc;
+    return download(out, dout.get(), (size_t)N * (size_t)L);
 }
 
 }  // extern "C"
@@ -581,9 +578,8 @@ int ldpc_dna_strands(const uint8_t* codewords, int32_t n_cw, int64_t N, const in
 // --- the centre-star alignment (star_align.hpp) ---------
 namespace {
 
-namespace star = ldpc::star;
+using namespace ldpc;
 
-constexpr int32_t kStarMaxLen = 800;               // device path: the DP row and the centre of 64 lanes in LDS
 constexpr int64_t kStarMaxGroup = 32768;           // reads per group (the host keeps a k x k distance matrix)
 constexpr int64_t kStarDefaultWs = 256ll << 20;    // workspace_bytes = 0
 
@@ -622,15 +618,9 @@ int star_args(const std::string& who, const StarCall& a)
     }
     if (a.out_needed) *a.out_needed = 0;
     int64_t total = 0;
-    for (int64_t i = 0; i < a.n_seqs; i++) {
-        if (a.lengths[i] < 0 || a.offsets[i] < 0 || a.offsets[i] > INT64_MAX - a.lengths[i]) {
-            set_error(who + ": negative or overflowing length/offset");
-            return LDPC_ERR_ARG;
-        }
-        if (a.lengths[i] > 0) total = std::max<int64_t>(total, a.offsets[i] + a.lengths[i]);
-    }
-    if (total > 0 && !a.seqs) {
-        set_error(who + ": null sequences");
+    const std::string err = ldpc::ragged::check(a.seqs, a.offsets, a.lengths, a.n_seqs, &total);
+    if (!err.empty()) {
+        set_error(who + ": " + err);
         return LDPC_ERR_ARG;
     }
     if (a.n_groups == 0 ? a.n_seqs != 0 : (a.group_ptr[0] != 0 || a.group_ptr[a.n_groups] != a.n_seqs)) {
@@ -731,14 +721,96 @@ int star_align_host(const StarCall& a)
     return star_finish(who, a, s);
 }
 
-// Workspace words of one lane-interleaved block: rows x words per row x 64 lanes.
-int64_t star_block_words(int64_t m, int64_t wpr) { return m * wpr * 64; }
+// The reads, resident for the device aligner; seqs is the caller's copy or own_seqs.
+struct StarDev {
+    dev_ptr<uint8_t> own_seqs;
+    const uint8_t* seqs = nullptr;
+    dev_ptr<int64_t> off;
+    dev_ptr<int32_t> len;
+};
+
+// The centres of the on-device groups of more than two reads: k_edit_distance
+// on all in-group pairs (k = 2: the tie goes to read 0, s->centre stays 0).
+int star_centres(const StarCall& a, const std::vector<uint8_t>& on_dev, const StarDev& d, int32_t max_len, StarScripts* s)
+{
+    std::vector<int32_t> pa, pb;
+    for (int64_t g = 0; g < a.n_groups; g++) {
+        const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
+        if (!on_dev[(size_t)g] || k <= 2) continue;
+        for (int64_t x = 0; x < k; x++)
+            for (int64_t y = x + 1; y < k; y++) {
+                pa.push_back((int32_t)(g0 + x));
+                pb.push_back((int32_t)(g0 + y));
+            }
+    }
+    const size_t np = pa.size();
+    if (np == 0) return LDPC_OK;
+    std::vector<int32_t> dist(np);
+    dev_ptr<int32_t> da, db, dd;
+    int rc;
+    if ((rc = upload(da, pa)) || (rc = upload(db, pb)) || (rc = dev_alloc(dd, np)) ||
+        (rc = launch_edit_distance(d.seqs, d.off.get(), d.len.get(), da.get(), db.get(), (int64_t)np, max_len,
+                                   dd.get())) ||
+        (rc = download(dist.data(), dd.get(), np)))
+        return rc;
+    const int32_t* dp = dist.data();
+    std::vector<int64_t> dm;
+    for (int64_t g = 0; g < a.n_groups; g++) {
+        const int64_t k = a.group_ptr[g + 1] - a.group_ptr[g];
+        if (!on_dev[(size_t)g] || k <= 2) continue;
+        dm.assign((size_t)(k * k), 0);
+        for (int64_t x = 0; x < k; x++)
+            for (int64_t y = x + 1; y < k; y++) dm[(size_t)(x * k + y)] = dm[(size_t)(y * k + x)] = *dp++;
+        s->centre[(size_t)g] = star::choose_centre(dm.data(), k);
+    }
+    return LDPC_OK;
+}
+
+// The scripts of the packed pairs as k_star_align_pairs leaves them.
+struct StarPairsOut {
+    std::vector<uint8_t> at, ins;
+    std::vector<int32_t> cnt, dist;
+};
+
+// k_star_align_pairs over the packed pairs, one launch per pass, and its outputs to the host.
+int star_run_pairs(const star::PairBlocks& pb, const star::Passes& ps, const StarDev& d, StarPairsOut* h)
+{
+    const size_t P = pb.pr.size(), n_at = (size_t)pb.at_total, n_ins = (size_t)pb.ins_total;
+    h->at.resize(n_at);
+    h->ins.resize(n_ins);
+    h->cnt.resize(n_at + P);
+    h->dist.resize(P);
+    if (P == 0) return LDPC_OK;
+    dev_ptr<int32_t> dpr, dpc, dbp, dcnt, ddist;
+    dev_ptr<int64_t> dbf, dbw, dao, dio;
+    dev_ptr<uint32_t> dws;
+    dev_ptr<uint8_t> dat, dins;
+    int rc;
+    if ((rc = upload(dpr, pb.pr)) || (rc = upload(dpc, pb.pc)) || (rc = upload(dbf, pb.blk_first)) ||
+        (rc = upload(dbw, ps.blk_ws)) || (rc = upload(dbp, pb.blk_wpr)) || (rc = upload(dao, pb.at_off)) ||
+        (rc = upload(dio, pb.ins_off)) || (rc = dev_alloc(dws, (size_t)ps.ws_words)) || (rc = dev_alloc(dat, n_at)) ||
+        (rc = dev_alloc(dcnt, n_at + P)) || (rc = dev_alloc(dins, n_ins)) || (rc = dev_alloc(ddist, P)))
+        return rc;
+    const size_t lds = (sizeof(uint16_t) * (size_t)(pb.max_n + 1) + (size_t)pb.max_n) * 64;
+    for (size_t q = 0; q + 1 < ps.pass_first.size(); q++) {
+        const int64_t b0 = ps.pass_first[q], nb = ps.pass_first[q + 1] - b0;
+        if ((rc = launch(k_star_align_pairs, dim3((unsigned)nb), dim3(64), lds, nullptr, d.seqs, d.off.get(), d.len.get(),
+                         dpr.get(), dpc.get(), dbf.get(), dbw.get(), dbp.get(), dao.get(), dio.get(), b0, pb.max_n,
+                         dws.get(), dat.get(), dcnt.get(), dins.get(), ddist.get())))
+            return rc;
+    }
+    if ((rc = download(h->at.data(), dat.get(), n_at)) || (rc = download(h->cnt.data(), dcnt.get(), n_at + P)) ||
+        (rc = download(h->ins.data(), dins.get(), n_ins)))
+        return rc;
+    return download(h->dist.data(), ddist.get(), P);
+}
 
 // dev_seqs (may be null): a.seqs already resident on `device` (the read planner's reads).
+// The planning (which groups, blocks, passes) is star_align.hpp's; here are the
+// uploads, the centre search, the pass loop and the downloads.
 int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes, int64_t* stats,
                       const std::string& who = "ldpc_dna_star_align", const uint8_t* dev_seqs = nullptr)
 {
-    using namespace ldpc;
     if (stats) stats[0] = stats[1] = stats[2] = 0;
     if (int rc = star_args(who, a)) return rc;
     if (workspace_bytes < 0) {
@@ -752,189 +824,56 @@ int star_align_device(const StarCall& a, int32_t device, int64_t workspace_bytes
     StarScripts s;
     star_scripts_init(a, &s);
     if (a.n_groups == 0) return star_finish(who, a, s);
-    if (int rc = select_device(who.c_str(), device)) return rc;
+    int rc;
+    if ((rc = select_device(who.c_str(), device))) return rc;
     const int64_t budget_words = (workspace_bytes ? workspace_bytes : kStarDefaultWs) / 4;
 
-    // groups the device takes: two reads or more, none longer than kStarMaxLen
+    // the groups the device takes, and the bytes of seqs they span
     std::vector<uint8_t> on_dev((size_t)a.n_groups, 0);
-    int64_t seq_bytes = 0, n_dist_pairs = 0;
+    int64_t seq_bytes = 0;
     int32_t max_len = 0;
     for (int64_t g = 0; g < a.n_groups; g++) {
         const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
-        bool ok = k >= 2;
-        for (int64_t q = g0; q < g0 + k && ok; q++) ok = a.lengths[q] <= kStarMaxLen;
-        on_dev[(size_t)g] = ok;
-        if (!ok) continue;
+        on_dev[(size_t)g] = star::device_eligible(a.lengths + g0, k);
+        if (!on_dev[(size_t)g]) continue;
         for (int64_t q = g0; q < g0 + k; q++) {
             max_len = std::max(max_len, a.lengths[q]);
             if (a.lengths[q]) seq_bytes = std::max<int64_t>(seq_bytes, a.offsets[q] + a.lengths[q]);
         }
-        if (k > 2) n_dist_pairs += k * (k - 1) / 2;
     }
-    dev_ptr<uint8_t> ds;
-    dev_ptr<int64_t> doff;
-    dev_ptr<int32_t> dlen;
-    int rc;
-    if (!dev_seqs && (rc = upload(ds, a.seqs, (size_t)seq_bytes))) return rc;
-    const uint8_t* d_seqs = dev_seqs ? dev_seqs : ds.get();
-    if ((rc = upload(doff, a.offsets, (size_t)a.n_seqs))) return rc;
-    if ((rc = upload(dlen, a.lengths, (size_t)a.n_seqs))) return rc;
-
-    // the centres: k_edit_distance on all in-group pairs (k = 2: the tie goes to read 0)
-    if (n_dist_pairs > 0) {
-        std::vector<int32_t> pa((size_t)n_dist_pairs), pb((size_t)n_dist_pairs), d((size_t)n_dist_pairs);
-        int64_t np = 0;
-        for (int64_t g = 0; g < a.n_groups; g++) {
-            const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
-            if (!on_dev[(size_t)g] || k <= 2) continue;
-            for (int64_t x = 0; x < k; x++)
-                for (int64_t y = x + 1; y < k; y++, np++) {
-                    pa[(size_t)np] = (int32_t)(g0 + x);
-                    pb[(size_t)np] = (int32_t)(g0 + y);
-                }
-        }
-        dev_ptr<int32_t> da, db, dd;
-        if ((rc = upload(da, pa.data(), (size_t)np))) return rc;
-        if ((rc = upload(db, pb.data(), (size_t)np))) return rc;
-        if ((rc = dev_alloc(dd, (size_t)np))) return rc;
-        if ((rc = launch_edit_distance(d_seqs, doff.get(), dlen.get(), da.get(),
-                                       db.get(), np, max_len, dd.get())))
-            return rc;
-        LDPC_HIP(hipMemcpy(d.data(), dd.get(), sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost));
-        np = 0;
-        std::vector<int64_t> dm;
-        for (int64_t g = 0; g < a.n_groups; g++) {
-            const int64_t k = a.group_ptr[g + 1] - a.group_ptr[g];
-            if (!on_dev[(size_t)g] || k <= 2) continue;
-            dm.assign((size_t)(k * k), 0);
-            for (int64_t x = 0; x < k; x++)
-                for (int64_t y = x + 1; y < k; y++, np++) dm[(size_t)(x * k + y)] = dm[(size_t)(y * k + x)] = d[(size_t)np];
-            s.centre[(size_t)g] = star::choose_centre(dm.data(), k);
-        }
-    }
-
-    // a group with a pair whose own block (64 lanes x m rows x ceil(n / 16) words) is
-    // beyond the budget goes to the host
+    StarDev d;
+    if ((!dev_seqs && (rc = upload(d.own_seqs, a.seqs, (size_t)seq_bytes))) ||
+        (rc = upload(d.off, a.offsets, (size_t)a.n_seqs)) || (rc = upload(d.len, a.lengths, (size_t)a.n_seqs)))
+        return rc;
+    d.seqs = dev_seqs ? dev_seqs : d.own_seqs.get();
+    if ((rc = star_centres(a, on_dev, d, max_len, &s))) return rc;
     for (int64_t g = 0; g < a.n_groups; g++) {
-        if (!on_dev[(size_t)g]) continue;
         const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
-        const int64_t wpr = ((int64_t)a.lengths[g0 + s.centre[(size_t)g]] + 15) / 16;
-        for (int64_t q = g0; q < g0 + k; q++)
-            if (q != g0 + s.centre[(size_t)g] && star_block_words(a.lengths[q], wpr) > budget_words) on_dev[(size_t)g] = 0;
+        if (on_dev[(size_t)g]) on_dev[(size_t)g] = star::within_budget(a.lengths + g0, k, s.centre[(size_t)g], budget_words);
     }
 
-    // the (read, centre) pairs, cut into blocks of at most 64 that fit the budget
-    std::vector<int32_t> pr, pc, blk_wpr;
-    std::vector<int64_t> at_off, ins_off, blk_first, blk_words;
-    int64_t at_total = 0, ins_total = 0, n_host = 0;
-    int32_t max_n = 0;
-    {
-        int64_t cnt = 0, bm = 0, bw = 0;
-        for (int64_t g = 0; g < a.n_groups; g++) {
-            const int64_t g0 = a.group_ptr[g], k = a.group_ptr[g + 1] - g0;
-            if (!on_dev[(size_t)g]) {
-                if (k >= 2) n_host++;
-                continue;
-            }
-            const int64_t c = g0 + s.centre[(size_t)g], n = a.lengths[c], wpr = (n + 15) / 16;
-            max_n = std::max(max_n, (int32_t)n);
-            for (int64_t q = g0; q < g0 + k; q++) {
-                if (q == c) continue;
-                const int64_t m = a.lengths[q];
-                if (cnt == 64 || (cnt > 0 && star_block_words(std::max(bm, m), std::max(bw, wpr)) > budget_words)) {
-                    blk_words.push_back(star_block_words(bm, bw));
-                    blk_wpr.push_back((int32_t)bw);
-                    cnt = bm = bw = 0;
-                }
-                if (cnt == 0) blk_first.push_back((int64_t)pr.size());
-                cnt++;
-                bm = std::max(bm, m);
-                bw = std::max(bw, wpr);
-                pr.push_back((int32_t)q);
-                pc.push_back((int32_t)c);
-                at_off.push_back(at_total);
-                ins_off.push_back(ins_total);
-                at_total += n;
-                ins_total += m;
-            }
-        }
-        if (cnt > 0) {
-            blk_words.push_back(star_block_words(bm, bw));
-            blk_wpr.push_back((int32_t)bw);
-        }
-        blk_first.push_back((int64_t)pr.size());
-    }
-    const int64_t P = (int64_t)pr.size(), NB = (int64_t)blk_words.size();
-    std::vector<uint8_t> h_at((size_t)at_total), h_ins((size_t)ins_total);
-    std::vector<int32_t> h_cnt((size_t)(at_total + P)), h_dist((size_t)P);
-    int64_t passes = 0;
-    if (P > 0) {
-        // the passes: runs of blocks whose pieces of the workspace fit the budget together
-        std::vector<int64_t> blk_ws((size_t)NB), pass_first;
-        int64_t acc = 0, ws_words = 0;
-        for (int64_t b = 0; b < NB; b++) {
-            if (b == 0 || acc + blk_words[(size_t)b] > budget_words) {
-                pass_first.push_back(b);
-                acc = 0;
-            }
-            blk_ws[(size_t)b] = acc;
-            acc += blk_words[(size_t)b];
-            ws_words = std::max(ws_words, acc);
-        }
-        pass_first.push_back(NB);
-        passes = (int64_t)pass_first.size() - 1;
-        dev_ptr<int32_t> dpr, dpc, dbp, dcnt, ddist;
-        dev_ptr<int64_t> dbf, dbw, dao, dio;
-        dev_ptr<uint32_t> dws;
-        dev_ptr<uint8_t> dat, dins;
-        if ((rc = upload(dpr, pr.data(), (size_t)P))) return rc;
-        if ((rc = upload(dpc, pc.data(), (size_t)P))) return rc;
-        if ((rc = upload(dbf, blk_first.data(), (size_t)(NB + 1)))) return rc;
-        if ((rc = upload(dbw, blk_ws.data(), (size_t)NB))) return rc;
-        if ((rc = upload(dbp, blk_wpr.data(), (size_t)NB))) return rc;
-        if ((rc = upload(dao, at_off.data(), (size_t)P))) return rc;
-        if ((rc = upload(dio, ins_off.data(), (size_t)P))) return rc;
-        if ((rc = dev_alloc(dws, (size_t)ws_words))) return rc;
-        if ((rc = dev_alloc(dat, (size_t)at_total))) return rc;
-        if ((rc = dev_alloc(dcnt, (size_t)(at_total + P)))) return rc;
-        if ((rc = dev_alloc(dins, (size_t)ins_total))) return rc;
-        if ((rc = dev_alloc(ddist, (size_t)P))) return rc;
-        const size_t lds = (sizeof(uint16_t) * (size_t)(max_n + 1) + (size_t)max_n) * 64;
-        for (int64_t q = 0; q < passes; q++) {
-            const int64_t b0 = pass_first[(size_t)q], nb = pass_first[(size_t)q + 1] - b0;
-            hipLaunchKernelGGL(k_star_align_pairs, dim3((unsigned)nb), dim3(64), lds, 0, d_seqs,
-                               doff.get(), dlen.get(), dpr.get(), dpc.get(),
-                               dbf.get(), dbw.get(), dbp.get(), dao.get(),
-                               dio.get(), b0, max_n, dws.get(), dat.get(), dcnt.get(),
-                               dins.get(), ddist.get());
-            LDPC_HIP(hipGetLastError());
-        }
-        if (at_total) LDPC_HIP(hipMemcpy(h_at.data(), dat.get(), (size_t)at_total, hipMemcpyDeviceToHost));
-        LDPC_HIP(hipMemcpy(h_cnt.data(), dcnt.get(), sizeof(int32_t) * (size_t)(at_total + P), hipMemcpyDeviceToHost));
-        if (ins_total) LDPC_HIP(hipMemcpy(h_ins.data(), dins.get(), (size_t)ins_total, hipMemcpyDeviceToHost));
-        LDPC_HIP(hipMemcpy(h_dist.data(), ddist.get(), sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost));
-    }
+    const star::PairBlocks pb = star::pack_pairs(a.lengths, a.group_ptr, a.n_groups, s.centre.data(), on_dev.data(),
+                                                 budget_words);
+    const star::Passes ps = star::cut_passes(pb.blk_words, budget_words);
+    const int64_t P = (int64_t)pb.pr.size();
+    StarPairsOut h;
+    if ((rc = star_run_pairs(pb, ps, d, &h))) return rc;
     for (int64_t p = 0; p < P; p++) {
-        const int64_t q = pr[(size_t)p], m = a.lengths[q], n = a.lengths[pc[(size_t)p]];
-        const int32_t* cnt = h_cnt.data() + at_off[(size_t)p] + p;
+        const int64_t q = pb.pr[(size_t)p], m = a.lengths[q], n = a.lengths[pb.pc[(size_t)p]];
+        const int32_t* cnt = h.cnt.data() + pb.at_off[(size_t)p] + p;
         int64_t t = 0;
-        bool ok = true;
-        for (int64_t j = 0; j <= n; j++) {
-            ok = ok && cnt[j] >= 0 && cnt[j] <= m;
-            t += cnt[j];
-        }
-        if (!ok || t > m) {
+        if (!star::script_consistent(cnt, m, n, &t)) {
             set_error(who + ": a device script is inconsistent with its read");
             return LDPC_ERR_DEVICE;
         }
-        s.rows[(size_t)q] = star::RowScript{h_at.data() + at_off[(size_t)p], cnt, h_ins.data() + ins_off[(size_t)p] + m - t};
-        s.dist[(size_t)q] = h_dist[(size_t)p];
+        s.rows[(size_t)q] = star::RowScript{h.at.data() + pb.at_off[(size_t)p], cnt, h.ins.data() + pb.ins_off[(size_t)p] + m - t};
+        s.dist[(size_t)q] = h.dist[(size_t)p];
     }
     for (int64_t g = 0; g < a.n_groups; g++)
         if (!on_dev[(size_t)g]) star_group_host(a, g, &s);
     if (stats) {
-        stats[0] = n_host;
-        stats[1] = passes;
+        stats[0] = pb.n_host;
+        stats[1] = (int64_t)ps.pass_first.size() - 1;
         stats[2] = P;
     }
     return star_finish(who, a, s);
@@ -950,12 +889,7 @@ int ldpc_dna_star_align_host(const uint8_t* seqs, const int64_t* offsets, const 
 {
     const StarCall a{seqs, offsets, lengths, n_seqs, group_ptr, n_groups, center, width,
                      out_ptr, out, out_capacity, out_needed, dist};
-    try {
-        return star_align_host(a);
-    } catch (const std::bad_alloc&) {
-        set_error("ldpc_dna_star_align_host: out of host memory");
-        return LDPC_ERR_DEVICE;
-    }
+    return dna_guard("ldpc_dna_star_align_host", [&] { return star_align_host(a); });
 }
 
 int ldpc_dna_star_align(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, int64_t n_seqs,
@@ -965,12 +899,7 @@ int ldpc_dna_star_align(const uint8_t* seqs, const int64_t* offsets, const int32
 {
     const StarCall a{seqs, offsets, lengths, n_seqs, group_ptr, n_groups, center, width,
                      out_ptr, out, out_capacity, out_needed, dist};
-    try {
-        return star_align_device(a, device, workspace_bytes, stats);
-    } catch (const std::bad_alloc&) {
-        set_error("ldpc_dna_star_align: out of host memory");
-        return LDPC_ERR_DEVICE;
-    }
+    return dna_guard("ldpc_dna_star_align", [&] { return star_align_device(a, device, workspace_bytes, stats); });
 }
 
 }  // extern "C"
@@ -1007,12 +936,10 @@ int llr_from_plan(const ldpc::PlanDev& pd, int32_t n_strands, int32_t payload_nt
     if ((rc = launch_dna_llr(pd.kind.get(), pd.row_ptr.get(), pd.rows.get(), pd.row_q.get(), n_strands, payload_nt,
                              llr_unit, dl.get(), dm.get(), dc.get(), dov.get())))
         return rc;
-    LDPC_HIP(hipMemcpy(llr, dl.get(), sizeof(double) * out_n, hipMemcpyDeviceToHost));
-    if (int_mask) LDPC_HIP(hipMemcpy(int_mask, dm.get(), out_n, hipMemcpyDeviceToHost));
+    if ((rc = download(llr, dl.get(), out_n)) || (int_mask && (rc = download(int_mask, dm.get(), out_n)))) return rc;
     if (codes) {
         int32_t ov = 0;
-        LDPC_HIP(hipMemcpy(codes, dc.get(), out_n, hipMemcpyDeviceToHost));
-        LDPC_HIP(hipMemcpy(&ov, dov.get(), sizeof ov, hipMemcpyDeviceToHost));
+        if ((rc = download(codes, dc.get(), out_n)) || (rc = download(&ov, dov.get(), 1))) return rc;
         *codes_exact = ov ? 0 : 1;
     }
     return LDPC_OK;
@@ -1092,17 +1019,14 @@ int ldpc_dna_plan_host(const uint8_t* seqs, const int64_t* offsets, const int32_
                        int32_t payload_nt, int32_t align, int32_t* kind, int64_t* row_ptr, uint8_t* rows,
                        int32_t* row_q, int64_t* stats)
 {
-    try {
+    return ldpc::dna_guard("ldpc_dna_plan_host", [&]() -> int {
         const std::string err = ldpc::plan::plan_host(plan_args(seqs, offsets, lengths, quals, n_reads, index_vals,
                                                                 strands, n_strands, payload_nt, align, kind, row_ptr,
                                                                 rows, row_q, stats));
         if (err.empty()) return LDPC_OK;
         set_error("ldpc_dna_plan_host: " + err);
         return LDPC_ERR_ARG;
-    } catch (const std::bad_alloc&) {
-        set_error("ldpc_dna_plan_host: out of host memory");
-        return LDPC_ERR_DEVICE;
-    }
+    });
 }
 
 int ldpc_dna_plan(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, const int32_t* quals,
@@ -1110,16 +1034,13 @@ int ldpc_dna_plan(const uint8_t* seqs, const int64_t* offsets, const int32_t* le
                   int32_t payload_nt, int32_t align, int32_t device, int64_t workspace_bytes, int32_t* kind,
                   int64_t* row_ptr, uint8_t* rows, int32_t* row_q, int64_t* stats)
 {
-    try {
+    return ldpc::dna_guard("ldpc_dna_plan", [&] {
         ldpc::PlanDev pd;
         return ldpc::plan_device("ldpc_dna_plan", plan_args(seqs, offsets, lengths, quals, n_reads, index_vals, strands,
                                                             n_strands, payload_nt, align, kind, row_ptr, rows, row_q,
                                                             stats),
                                  true, device, workspace_bytes, &pd);
-    } catch (const std::bad_alloc&) {
-        set_error("ldpc_dna_plan: out of host memory");
-        return LDPC_ERR_DEVICE;
-    }
+    });
 }
 
 int ldpc_dna_reads_llr(const uint8_t* seqs, const int64_t* offsets, const int32_t* lengths, const int32_t* quals,
@@ -1128,14 +1049,11 @@ int ldpc_dna_reads_llr(const uint8_t* seqs, const int64_t* offsets, const int32_
                        double* llr, uint8_t* int_mask, int8_t* codes, int32_t* codes_exact, int32_t* kind,
                        int64_t* stats)
 {
-    try {
+    return ldpc::dna_guard("ldpc_dna_reads_llr", [&] {
         return reads_llr(plan_args(seqs, offsets, lengths, quals, n_reads, index_vals, strands, n_strands, payload_nt,
                                    align, kind, nullptr, nullptr, nullptr, stats),
                          device, workspace_bytes, llr_unit, llr, int_mask, codes, codes_exact);
-    } catch (const std::bad_alloc&) {
-        set_error("ldpc_dna_reads_llr: out of host memory");
-        return LDPC_ERR_DEVICE;
-    }
+    });
 }
 
 }  // extern "C"

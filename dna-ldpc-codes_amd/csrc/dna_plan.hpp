@@ -2,8 +2,8 @@
 // kind / row_ptr / rows / row_q plan that ldpc_dna_llr consumes, i.e. the
 // control flow of ex_decoder/decoder.py:103-497 that dna_llr.plan_llr mirrors
 // in Python.  Header-only host C++, no HIP: the body of ldpc_dna_plan_host,
-// the CPU-testable definition of the contract the kernels of dna_plan.hip
-// reproduce byte for byte, and what tests/dna_plan_san/plan_check.cpp includes.
+// the CPU-testable definition of the contract the kernels of
+// dna_plan_kernels.hpp reproduce byte for byte, and what tests/dna_plan_san/plan_check.cpp includes.
 //
 // Contract.
 //   reads     read i is seqs[offsets[i] .. offsets[i] + lengths[i]) with quality
@@ -38,6 +38,7 @@
 #include <string>
 #include <vector>
 
+#include "ragged_reads.hpp"
 #include "rs_index.hpp"
 #include "star_align.hpp"
 
@@ -88,13 +89,16 @@ inline std::string check_args(const Args& a, int64_t* total, bool plan_outputs =
         return "null kind, row_ptr, rows or row_q";
     for (int32_t s = 1; s < a.n_strands; s++)
         if (a.strands[s] <= a.strands[s - 1]) return "strands must be strictly ascending";
-    for (int64_t i = 0; i < a.n_reads; i++) {
-        if (a.lengths[i] < 0 || a.offsets[i] < 0 || a.offsets[i] > INT64_MAX - a.lengths[i])
-            return "negative or overflowing length/offset";
-        if (a.lengths[i] > 0) *total = std::max<int64_t>(*total, a.offsets[i] + a.lengths[i]);
-    }
-    if (*total > 0 && !a.seqs) return "null sequences";
-    return std::string();
+    return ragged::check(a.seqs, a.offsets, a.lengths, a.n_reads, total);
+}
+
+// What a candidate's aligned row (width bytes) leaves in its plan row dst[nt],
+// prefilled with '-': the row when width == nt, for any other width its last
+// byte in byte 0 (nothing for width 0).
+inline void aligned_row(const uint8_t* row, int64_t width, int32_t nt, uint8_t* dst)
+{
+    if (width == nt) std::memcpy(dst, row, (size_t)nt);
+    else if (width > 0) dst[0] = row[width - 1];
 }
 
 // Position of index value v in strands, or -1.
@@ -224,9 +228,7 @@ inline std::string plan_host(const Args& a)
             star::merge_rows(rs_.data(), nc, c, rd[(size_t)c], ln[(size_t)c], w, width, merged.data());
             a.kind[s] = width == nt ? 1 : 3;
             for (int64_t q = 0; q < nc; q++) {
-                uint8_t* row = a.rows + (size_t)(r0 + q) * (size_t)nt;
-                if (width == nt) std::memcpy(row, merged.data() + (size_t)(q * width), (size_t)nt);
-                else if (width > 0) row[0] = merged[(size_t)(q * width + width - 1)];
+                aligned_row(merged.data() + (size_t)(q * width), width, nt, a.rows + (size_t)(r0 + q) * (size_t)nt);
                 a.row_q[r0 + q] = a.quals[cand[(size_t)(c0 + q)]];
             }
         } else if (a.kind[s] == 1) {

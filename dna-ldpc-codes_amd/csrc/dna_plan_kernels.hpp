@@ -1,5 +1,7 @@
 // dna_plan_kernels.hpp -- the read planner on the GPU:
-// the kernels and the host driver of ldpc_dna_plan / ldpc_dna_reads_llr.
+// the kernels and the host driver of ldpc_dna_plan / ldpc_dna_reads_llr,
+// plan_device: a list of stages (plan_source .. plan_outputs, after the
+// kernels) over one work struct, PlanWork.
 // Included by dna.hip after its own kernels (k_rs_index_decode,
 // k_edit_distance, k_dna_llr) and the device aligner, which the driver reuses
 // on device-resident buffers.  The contract is dna_plan.hpp's; plan::plan_host
@@ -26,6 +28,7 @@
 //                      the range check of the reads, and the candidates packed
 //                      for the one copy down the aligner's host merge needs
 //   star_align_device  (dna.hip) on the resident reads; the merge is host code
+//                      and the rows it leaves in the plan are plan::aligned_row's
 //   k_plan_rows        one wave per row: rows, row_q, the kinds of aligned strands
 #pragma once
 
@@ -449,6 +452,316 @@ __global__ void __launch_bounds__(256) k_plan_cand_gather(const int32_t* __restr
     for (int64_t j = lane; j < l; j += 64) out[d + j] = seqs[o + skip + j];
 }
 
+// What plan_device keeps from stage to stage: the call, the device buffers
+// that live to its end (PlanDev's outlive it) and the control words read back.
+struct PlanWork {
+    const std::string& who;
+    const plan::Args& a;
+    const PlanSrc* src;
+    PlanDev* pd;
+    int32_t device;
+    int64_t workspace_bytes;
+    int64_t n;  // reads
+    int32_t S, nt;
+    dim3 per_read, per_strand;
+    // the reads: uploads (own_*) or the PlanSrc's
+    dev_ptr<uint8_t> own_seq;
+    dev_ptr<int64_t> own_off;
+    dev_ptr<int32_t> own_len, own_q;
+    const uint8_t* seq = nullptr;
+    const int64_t* off = nullptr;
+    const int32_t* len = nullptr;
+    const int32_t* q = nullptr;
+    dev_ptr<int32_t> strands, index, cnumerr;
+    dev_ptr<PlanCtl> dctl;
+    // per read: strand position and payload view; then the same in segment order
+    dev_ptr<int32_t> pos, plen, tmp, ids, slen;
+    dev_ptr<int64_t> poff, soff;
+    // per strand: counts, not-full flags, scatter cursors ([3][S]); segment, pair and candidate starts
+    dev_ptr<int32_t> cnt;
+    dev_ptr<int64_t> start, pstart, cptr, npairs, rowcnt, ncand;
+    dev_ptr<uint8_t> close, arows;
+    dev_ptr<int32_t> cand, width;
+    PlanCtl ctl{};
+    int64_t n_valid = 0, P = 0, C = 0, R = 0, n_aligned = 0;
+    std::vector<int32_t> h_width;  // aligned width per strand
+
+    int32_t* notfull() const { return cnt.get() + S; }
+    int32_t* cursor() const { return cnt.get() + 2 * (size_t)S; }
+    int inconsistent() const
+    {
+        set_error(who + ": the device plan is inconsistent");
+        return LDPC_ERR_DEVICE;
+    }
+};
+
+template <class T>
+int plan_scan(const T* in, int64_t n, int64_t* out)
+{
+    return launch(k_plan_scan<T>, dim3(1), dim3(kPlanScanThreads), 0, nullptr, in, n, out);
+}
+
+// The reads on the device (uploads, or the PlanSrc after its range check), the
+// strand list and the control block.
+int plan_source(PlanWork& w, int64_t total)
+{
+    const plan::Args& a = w.a;
+    const PlanSrc* src = w.src;
+    int rc;
+    if (!src && ((rc = upload(w.own_seq, a.seqs, (size_t)total)) || (rc = upload(w.own_off, a.offsets, (size_t)w.n)) ||
+                 (rc = upload(w.own_len, a.lengths, (size_t)w.n)) || (rc = upload(w.own_q, a.quals, (size_t)w.n))))
+        return rc;
+    w.seq = src ? src->seqs : w.own_seq.get();
+    w.off = src ? src->offsets : w.own_off.get();
+    w.len = src ? src->lengths : w.own_len.get();
+    w.q = src ? src->quals : w.own_q.get();
+    w.ctl.long_read = INT32_MAX;
+    w.ctl.empty_strand = INT32_MAX;
+    if ((rc = upload(w.strands, a.strands, (size_t)w.S)) || (rc = upload(w.dctl, &w.ctl, 1))) return rc;
+    if (!src) return LDPC_OK;
+    // before any kernel follows an offset
+    if (src->seq_bytes < 0 || (w.n > 0 && (!src->seqs || !src->offsets || !src->lengths || !src->quals))) {
+        set_error(w.who + ": bad device-resident reads");
+        return LDPC_ERR_ARG;
+    }
+    int32_t bad = 0;
+    if ((rc = launch(k_plan_check_src, w.per_read, dim3(256), 0, nullptr, w.off, w.len, w.n, src->seq_bytes, src->bad,
+                     w.dctl.get())) ||
+        (rc = download(&bad, &w.dctl.get()->bad, 1)))
+        return rc;
+    if (bad) {
+        set_error(w.who + ": the device-resident reads failed their range check");
+        return LDPC_ERR_DEVICE;
+    }
+    return LDPC_OK;
+}
+
+// Index values (the caller's, or k_rs_index_decode's), then locate, scan,
+// place and sort: strand s holds ids[start[s] .. start[s + 1]) in input order.
+int plan_segments(PlanWork& w)
+{
+    const plan::Args& a = w.a;
+    const int64_t n = w.n;
+    const int32_t S = w.S;
+    const size_t nn = (size_t)std::max<int64_t>(n, 1), SS = (size_t)S;
+    const dim3 b256(256);
+    int rc;
+    if (a.index_vals) {
+        if ((rc = upload(w.index, a.index_vals, (size_t)n))) return rc;
+    } else if ((rc = dev_alloc(w.index, nn)) || (rc = dev_alloc(w.cnumerr, nn)) ||
+               (n > 0 && (rc = launch(k_rs_index_decode, w.per_read, b256, 0, nullptr, w.seq, w.off, w.len, n,
+                                      w.index.get(), w.cnumerr.get())))) {
+        return rc;
+    }
+    if ((rc = dev_alloc(w.pos, nn)) || (rc = dev_alloc(w.poff, nn)) || (rc = dev_alloc(w.plen, nn)) ||
+        (rc = dev_alloc(w.tmp, nn)) || (rc = dev_alloc(w.ids, nn)) || (rc = dev_alloc(w.soff, nn)) ||
+        (rc = dev_alloc(w.slen, nn)) || (rc = dev_alloc(w.cnt, SS * 3)))
+        return rc;
+    LDPC_HIP(hipMemset(w.cnt.get(), 0, sizeof(int32_t) * SS * 3));
+    if ((rc = dev_alloc(w.start, SS + 1)) || (rc = dev_alloc(w.pstart, SS + 1)) || (rc = dev_alloc(w.cptr, SS + 1)) ||
+        (rc = dev_alloc(w.pd->row_ptr, SS + 1)) || (rc = dev_alloc(w.npairs, SS)) || (rc = dev_alloc(w.rowcnt, SS)) ||
+        (rc = dev_alloc(w.ncand, SS)) || (rc = dev_alloc(w.pd->kind, SS)))
+        return rc;
+    if (n > 0 && (rc = launch(k_plan_locate, w.per_read, b256, 0, nullptr, w.index.get(), w.cnumerr.get(), w.off, w.len, n,
+                              w.strands.get(), S, w.nt, w.pos.get(), w.poff.get(), w.plen.get(), w.cnt.get(),
+                              w.notfull(), w.dctl.get())))
+        return rc;
+    if ((rc = plan_scan(w.cnt.get(), (int64_t)S, w.start.get()))) return rc;
+    if (n > 0 && (rc = launch(k_plan_place, w.per_read, b256, 0, nullptr, w.pos.get(), n, S, w.start.get(), w.cursor(),
+                              w.tmp.get(), w.dctl.get())))
+        return rc;
+    return launch(k_plan_sort, dim3(plan_blocks((int64_t)S * 8, 256)), b256, 0, nullptr, w.tmp.get(), w.start.get(), S, n,
+                  w.poff.get(), w.plen.get(), w.ids.get(), w.soff.get(), w.slen.get(), w.dctl.get());
+}
+
+// Kinds, pair counts and provisional row counts; then the first look at the
+// control words: n_valid, P and what the kernels flagged.
+int plan_classify(PlanWork& w)
+{
+    const std::string& who = w.who;
+    const int32_t S = w.S;
+    int rc;
+    if ((rc = launch(k_plan_classify, w.per_strand, dim3(256), 0, nullptr, w.start.get(), S, w.n, w.notfull(),
+                     w.ids.get(), w.slen.get(), w.q, w.nt, w.pd->kind.get(), w.npairs.get(), w.rowcnt.get(),
+                     w.dctl.get())) ||
+        (rc = plan_scan(w.npairs.get(), (int64_t)S, w.pstart.get())) || (rc = download(&w.ctl, w.dctl.get(), 1)) ||
+        (rc = download(&w.n_valid, w.start.get() + S, 1)) || (rc = download(&w.P, w.pstart.get() + S, 1)))
+        return rc;
+    if (w.ctl.bad || w.n_valid < 0 || w.n_valid > w.n || w.P < 0) return w.inconsistent();
+    if (w.ctl.empty_strand != INT32_MAX) {
+        set_error(who + ": empty read on strand " + std::to_string(w.ctl.empty_strand) +
+                  " with quality > 63 (the reference indexes its last bit)");
+        return LDPC_ERR_ARG;
+    }
+    if (w.ctl.long_read != INT32_MAX) {
+        set_error(who + ": read " + std::to_string(w.ctl.long_read) + " on a ragged strand is longer than " +
+                  std::to_string(kPlanMaxLen) + " bytes (ldpc_dna_plan_host has no such limit)");
+        return LDPC_ERR_ARG;
+    }
+    if (w.P > (int64_t)INT32_MAX * 64) {
+        set_error(who + ": too many distance pairs for one call");
+        return LDPC_ERR_UNSUPPORTED;
+    }
+    return LDPC_OK;
+}
+
+// The pairs of the ragged strands, their distances, and the reads with a close partner.
+int plan_close_reads(PlanWork& w)
+{
+    const int64_t P = w.P;
+    const size_t n_close = (size_t)std::max<int64_t>(w.n_valid, 16);
+    const dim3 b256(256), per_pair(plan_blocks(P, 256));
+    int rc;
+    if ((rc = dev_alloc(w.close, n_close))) return rc;
+    LDPC_HIP(hipMemset(w.close.get(), 0, n_close));
+    if (P == 0) return LDPC_OK;
+    dev_ptr<int32_t> pa, pb, dist;
+    if ((rc = dev_alloc(pa, (size_t)P)) || (rc = dev_alloc(pb, (size_t)P)) || (rc = dev_alloc(dist, (size_t)P)) ||
+        (rc = launch(k_plan_pairs, per_pair, b256, 0, nullptr, w.pstart.get(), w.start.get(), w.S, w.n_valid, P, pa.get(),
+                     pb.get(), w.dctl.get())) ||
+        (rc = launch_edit_distance(w.seq, w.soff.get(), w.slen.get(), pa.get(), pb.get(), P,
+                                   std::max(w.ctl.max_ragged_len, 0), dist.get())))
+        return rc;
+    return launch(k_plan_close, per_pair, b256, 0, nullptr, pa.get(), pb.get(), dist.get(), P, w.n_valid, w.close.get(),
+                  w.dctl.get());
+}
+
+// Candidates per strand, candidate starts and row_ptr; C and R; the candidate list.
+int plan_candidates(PlanWork& w)
+{
+    const int32_t S = w.S;
+    const dim3 b256(256);
+    int rc;
+    if ((rc = launch(k_plan_cand_count, w.per_strand, b256, 0, nullptr, w.start.get(), S, w.n_valid, w.npairs.get(),
+                     w.close.get(), w.ncand.get(), w.rowcnt.get())) ||
+        (rc = plan_scan(w.ncand.get(), (int64_t)S, w.cptr.get())) ||
+        (rc = plan_scan(w.rowcnt.get(), (int64_t)S, w.pd->row_ptr.get())) ||
+        (rc = download(&w.C, w.cptr.get() + S, 1)) || (rc = download(&w.R, w.pd->row_ptr.get() + S, 1)))
+        return rc;
+    if (w.C < 0 || w.C > w.n_valid || w.R < 0 || w.R > w.n_valid) return w.inconsistent();
+    if ((rc = dev_alloc(w.cand, (size_t)w.C))) return rc;
+    if (w.C == 0) return LDPC_OK;
+    if (!w.a.align) {
+        set_error(w.who + ": ragged strands need an aligner (align = 0)");
+        return LDPC_ERR_ARG;
+    }
+    return launch(k_plan_cand_fill, w.per_strand, b256, 0, nullptr, w.start.get(), S, w.n_valid, w.cptr.get(), w.C,
+                  w.close.get(), w.ids.get(), w.cand.get(), w.dctl.get());
+}
+
+// The aligner's view of the candidates of host reads: offsets and lengths into a.seqs.
+int plan_cands_host(const PlanWork& w, const std::vector<int32_t>& cand, int64_t skip, std::vector<int64_t>* coff,
+                    std::vector<int32_t>* clen)
+{
+    for (int64_t c = 0; c < w.C; c++) {
+        const int32_t r = cand[(size_t)c];
+        if (r < 0 || r >= w.n || w.a.lengths[r] < skip) return w.inconsistent();
+        (*coff)[(size_t)c] = w.a.offsets[r] + skip;
+        (*clen)[(size_t)c] = (int32_t)(w.a.lengths[r] - skip);
+    }
+    return LDPC_OK;
+}
+
+// ... and of device-resident reads: the candidates' payloads packed by
+// k_plan_cand_gather into *dcseq, and copied down into *cseq for the host merge.
+int plan_cands_device(PlanWork& w, int64_t skip, std::vector<int64_t>* coff, std::vector<int32_t>* clen,
+                      std::vector<uint8_t>* cseq, dev_ptr<uint8_t>* dcseq)
+{
+    const int64_t C = w.C;
+    const dim3 b256(256);
+    dev_ptr<int32_t> dclen;
+    dev_ptr<int64_t> dcoff;
+    int64_t T = 0;
+    int rc;
+    if ((rc = dev_alloc(dclen, (size_t)C)) || (rc = dev_alloc(dcoff, (size_t)C + 1)) ||
+        (rc = launch(k_plan_cand_len, dim3(plan_blocks(C, 256)), b256, 0, nullptr, w.cand.get(), C, w.n, w.len,
+                     (int32_t)skip, dclen.get(), w.dctl.get())) ||
+        (rc = plan_scan(dclen.get(), C, dcoff.get())) || (rc = download(&T, dcoff.get() + C, 1)))
+        return rc;
+    if (T < 0 || T > C * (int64_t)kPlanMaxLen) return w.inconsistent();
+    cseq->resize((size_t)T);
+    if ((rc = dev_alloc(*dcseq, (size_t)T)) ||
+        (rc = launch(k_plan_cand_gather, dim3(plan_blocks(C, 4)), b256, 0, nullptr, w.cand.get(), C, w.n, w.seq, w.off,
+                     w.src->seq_bytes, (int32_t)skip, dcoff.get(), dclen.get(), T, dcseq->get(), w.dctl.get())) ||
+        (rc = download(coff->data(), dcoff.get(), (size_t)C)) || (rc = download(clen->data(), dclen.get(), (size_t)C)) ||
+        (rc = download(cseq->data(), dcseq->get(), (size_t)T)) || (rc = download(&w.ctl, w.dctl.get(), 1)))
+        return rc;
+    return w.ctl.bad ? w.inconsistent() : LDPC_OK;
+}
+
+// The aligner: group s = the candidates of strand s (empty for most strands);
+// its rows become the planner's (plan::aligned_row) and go up for k_plan_rows.
+int plan_align(PlanWork& w)
+{
+    const int32_t S = w.S, nt = w.nt;
+    const int64_t C = w.C, skip = w.a.index_vals ? 0 : rs::kPrefixNt;
+    std::vector<int64_t> cptr((size_t)S + 1), coff((size_t)C), out_ptr((size_t)S + 1);
+    std::vector<int32_t> cand((size_t)C), clen((size_t)C), centre((size_t)S);
+    std::vector<uint8_t> out, cseq;  // cseq / dcseq, device source: the candidates' payloads, packed
+    dev_ptr<uint8_t> dcseq;
+    int rc;
+    if ((rc = download(cptr.data(), w.cptr.get(), (size_t)S + 1)) || (rc = download(cand.data(), w.cand.get(), (size_t)C)))
+        return rc;
+    if (cptr[0] != 0 || cptr[(size_t)S] != C) return w.inconsistent();
+    if ((rc = w.src ? plan_cands_device(w, skip, &coff, &clen, &cseq, &dcseq) : plan_cands_host(w, cand, skip, &coff, &clen)))
+        return rc;
+    StarCall sc{w.src ? cseq.data() : w.a.seqs, coff.data(), clen.data(), C, cptr.data(), (int64_t)S, centre.data(),
+                w.h_width.data(), out_ptr.data(), nullptr, 0, nullptr, nullptr};
+    sc.out_vec = &out;
+    if ((rc = star_align_device(sc, w.device, w.workspace_bytes, nullptr, w.who, w.src ? dcseq.get() : w.seq))) return rc;
+    std::vector<uint8_t> arows((size_t)C * (size_t)nt, star::kGap);
+    for (int32_t s = 0; s < S; s++) {
+        const int64_t c0 = cptr[(size_t)s], nc = cptr[(size_t)s + 1] - c0, wd = w.h_width[(size_t)s];
+        if (nc == 0) continue;
+        w.n_aligned++;
+        for (int64_t q = 0; q < nc; q++)
+            plan::aligned_row(out.data() + out_ptr[(size_t)s] + q * wd, wd, nt, arows.data() + (size_t)(c0 + q) * (size_t)nt);
+    }
+    return upload(w.arows, arows);
+}
+
+// k_plan_rows: rows and row_q, and the kinds of the aligned strands; the last look at the flag.
+int plan_rows(PlanWork& w)
+{
+    PlanDev* pd = w.pd;
+    const int64_t R = w.R;
+    int rc;
+    if ((rc = upload(w.width, w.h_width)) || (rc = dev_alloc(pd->rows, (size_t)R * (size_t)w.nt)) ||
+        (rc = dev_alloc(pd->row_q, (size_t)R)) ||
+        (R > 0 && (rc = launch(k_plan_rows, dim3((unsigned)std::min<int64_t>((R + 3) / 4, 2048)), dim3(256), 0, nullptr,
+                               pd->row_ptr.get(), w.S, R, w.start.get(), w.n_valid, w.n, w.cptr.get(), w.C, w.cand.get(),
+                               w.arows.get(), w.width.get(), w.seq, w.soff.get(), w.slen.get(), w.ids.get(), w.q, w.nt,
+                               pd->kind.get(), pd->rows.get(), pd->row_q.get(), w.dctl.get()))) ||
+        (rc = download(&w.ctl, w.dctl.get(), 1)))
+        return rc;
+    if (w.ctl.bad) return w.inconsistent();
+    pd->R = R;
+    return LDPC_OK;
+}
+
+// The host outputs the caller asked for, and the stats.
+int plan_outputs(const PlanWork& w, bool host_outputs)
+{
+    const plan::Args& a = w.a;
+    const PlanDev& pd = *w.pd;
+    const size_t SS = (size_t)w.S, R = (size_t)w.R;
+    int rc;
+    if (a.kind && (rc = download(a.kind, pd.kind.get(), SS))) return rc;
+    if (host_outputs && ((rc = download(a.row_ptr, pd.row_ptr.get(), SS + 1)) ||
+                         (rc = download(a.rows, pd.rows.get(), R * (size_t)w.nt)) ||
+                         (rc = download(a.row_q, pd.row_q.get(), R))))
+        return rc;
+    if (a.stats) {
+        a.stats[plan::kStatValid] = w.n_valid;
+        a.stats[plan::kStatPairs] = w.P;
+        a.stats[plan::kStatAligned] = w.n_aligned;
+        a.stats[plan::kStatAlignPairs] = w.C - w.n_aligned;
+        a.stats[plan::kStatRows] = w.R;
+        for (int k = 0; k < 4; k++) a.stats[plan::kStatCnumerr + k] = (int64_t)w.ctl.hist[k];
+    }
+    return LDPC_OK;
+}
+
 // The device planner.  Host outputs of `a` that are null are skipped (the
 // fused call passes none but kind / stats).  With `src` the reads are the
 // device-resident ones (a.seqs / offsets / lengths / quals are not read): the
@@ -471,298 +784,26 @@ int plan_device(const std::string& who, const plan::Args& a, bool host_outputs, 
         set_error(who + ": negative workspace_bytes");
         return LDPC_ERR_ARG;
     }
-    const int64_t n = a.n_reads;
-    const int32_t S = a.n_strands, nt = a.payload_nt;
-    if (n > INT32_MAX - 1024) {
+    if (a.n_reads > INT32_MAX - 1024) {
         set_error(who + ": too many reads for one call");
         return LDPC_ERR_UNSUPPORTED;
     }
     if (a.stats) std::fill(a.stats, a.stats + plan::kNumStats, 0);
-    if (S == 0) {
+    if (a.n_strands == 0) {
         if (host_outputs) a.row_ptr[0] = 0;
         pd->R = 0;
         return LDPC_OK;
     }
-    if (int rc = select_device(who.c_str(), device)) return rc;
-
-    const size_t nn = (size_t)std::max<int64_t>(n, 1), SS = (size_t)S;
-    dev_ptr<uint8_t> dseq;
-    dev_ptr<int64_t> doff, dpoff, dstart, dsoff, dnp, drc, dpstart, dncand, dcptr;
-    dev_ptr<int32_t> dlen, dq, dstr, div, dne, dpos, dplen, dcnt, dtmp, dids, dslen;
-    dev_ptr<PlanCtl> dctl;
     int rc;
-    if (!src) {
-        if ((rc = upload(dseq, a.seqs, (size_t)total))) return rc;
-        if ((rc = upload(doff, a.offsets, (size_t)n))) return rc;
-        if ((rc = upload(dlen, a.lengths, (size_t)n))) return rc;
-        if ((rc = upload(dq, a.quals, (size_t)n))) return rc;
-    }
-    const uint8_t* d_seq = src ? src->seqs : dseq.get();
-    const int64_t* d_off = src ? src->offsets : doff.get();
-    const int32_t* d_len = src ? src->lengths : dlen.get();
-    const int32_t* d_q = src ? src->quals : dq.get();
-    if ((rc = upload(dstr, a.strands, SS))) return rc;
-    PlanCtl ctl{};
-    ctl.long_read = INT32_MAX;
-    ctl.empty_strand = INT32_MAX;
-    if ((rc = upload(dctl, &ctl, 1))) return rc;
-    if (src) {  // before any kernel follows an offset
-        if (src->seq_bytes < 0 || (n > 0 && (!src->seqs || !src->offsets || !src->lengths || !src->quals))) {
-            set_error(who + ": bad device-resident reads");
-            return LDPC_ERR_ARG;
-        }
-        int32_t bad = 0;
-        hipLaunchKernelGGL(k_plan_check_src, dim3(plan_blocks(n, 256)), dim3(256), 0, 0, d_off, d_len, n,
-                           src->seq_bytes, src->bad, dctl.get());
-        LDPC_HIP(hipGetLastError());
-        LDPC_HIP(hipMemcpy(&bad, &dctl.get()->bad, sizeof bad, hipMemcpyDeviceToHost));
-        if (bad) {
-            set_error(who + ": the device-resident reads failed their range check");
-            return LDPC_ERR_DEVICE;
-        }
-    }
-    if (a.index_vals) {
-        if ((rc = upload(div, a.index_vals, (size_t)n))) return rc;
-    } else {
-        if ((rc = dev_alloc(div, nn))) return rc;
-        if ((rc = dev_alloc(dne, nn))) return rc;
-        if (n > 0) {
-            hipLaunchKernelGGL(k_rs_index_decode, dim3(plan_blocks(n, 256)), dim3(256), 0, 0, d_seq,
-                               d_off, d_len, n, div.get(), dne.get());
-            LDPC_HIP(hipGetLastError());
-        }
-    }
-    if ((rc = dev_alloc(dpos, nn))) return rc;
-    if ((rc = dev_alloc(dpoff, nn))) return rc;
-    if ((rc = dev_alloc(dplen, nn))) return rc;
-    if ((rc = dev_alloc(dtmp, nn))) return rc;
-    if ((rc = dev_alloc(dids, nn))) return rc;
-    if ((rc = dev_alloc(dsoff, nn))) return rc;
-    if ((rc = dev_alloc(dslen, nn))) return rc;
-    if ((rc = dev_alloc(dcnt, SS * 3))) return rc;  // counts, not-full flags, scatter cursors
-    LDPC_HIP(hipMemset(dcnt.get(), 0, sizeof(int32_t) * SS * 3));
-    int32_t* d_cnt = dcnt.get();
-    int32_t* d_notfull = d_cnt + SS;
-    int32_t* d_cursor = d_cnt + 2 * SS;
-    if ((rc = dev_alloc(dstart, (SS + 1)))) return rc;
-    if ((rc = dev_alloc(dpstart, (SS + 1)))) return rc;
-    if ((rc = dev_alloc(dcptr, (SS + 1)))) return rc;
-    if ((rc = dev_alloc(pd->row_ptr, (SS + 1)))) return rc;
-    if ((rc = dev_alloc(dnp, SS))) return rc;
-    if ((rc = dev_alloc(drc, SS))) return rc;
-    if ((rc = dev_alloc(dncand, SS))) return rc;
-    if ((rc = dev_alloc(pd->kind, SS))) return rc;
-    PlanCtl* d_ctl = dctl.get();
-    const dim3 b256(256), per_read(plan_blocks(n, 256)), per_strand(plan_blocks(S, 256));
-
-    if (n > 0) {
-        hipLaunchKernelGGL(k_plan_locate, per_read, b256, 0, 0, div.get(),
-                           a.index_vals ? nullptr : dne.get(), d_off, d_len, n,
-                           dstr.get(), S, nt, dpos.get(), dpoff.get(), dplen.get(),
-                           d_cnt, d_notfull, d_ctl);
-        LDPC_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_plan_scan<int32_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, d_cnt, (int64_t)S,
-                       dstart.get());
-    LDPC_HIP(hipGetLastError());
-    if (n > 0) {
-        hipLaunchKernelGGL(k_plan_place, per_read, b256, 0, 0, dpos.get(), n, S, dstart.get(), d_cursor,
-                           dtmp.get(), d_ctl);
-        LDPC_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_plan_sort, dim3(plan_blocks((int64_t)S * 8, 256)), b256, 0, 0, dtmp.get(),
-                       dstart.get(), S, n, dpoff.get(), dplen.get(), dids.get(),
-                       dsoff.get(), dslen.get(), d_ctl);
-    LDPC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_plan_classify, per_strand, b256, 0, 0, dstart.get(), S, n, d_notfull,
-                       dids.get(), dslen.get(), d_q, nt, pd->kind.get(),
-                       dnp.get(), drc.get(), d_ctl);
-    LDPC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_plan_scan<int64_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, dnp.get(), (int64_t)S,
-                       dpstart.get());
-    LDPC_HIP(hipGetLastError());
-
-    int64_t n_valid = 0, P = 0;
-    LDPC_HIP(hipMemcpy(&ctl, dctl.get(), sizeof ctl, hipMemcpyDeviceToHost));
-    LDPC_HIP(hipMemcpy(&n_valid, dstart.get() + S, sizeof n_valid, hipMemcpyDeviceToHost));
-    LDPC_HIP(hipMemcpy(&P, dpstart.get() + S, sizeof P, hipMemcpyDeviceToHost));
-    if (ctl.bad || n_valid < 0 || n_valid > n || P < 0) {
-        set_error(who + ": the device plan is inconsistent");
-        return LDPC_ERR_DEVICE;
-    }
-    if (ctl.empty_strand != INT32_MAX) {
-        set_error(who + ": empty read on strand " + std::to_string(ctl.empty_strand) +
-                  " with quality > 63 (the reference indexes its last bit)");
-        return LDPC_ERR_ARG;
-    }
-    if (ctl.long_read != INT32_MAX) {
-        set_error(who + ": read " + std::to_string(ctl.long_read) + " on a ragged strand is longer than " +
-                  std::to_string(kPlanMaxLen) + " bytes (ldpc_dna_plan_host has no such limit)");
-        return LDPC_ERR_ARG;
-    }
-    if (P > (int64_t)INT32_MAX * 64) {
-        set_error(who + ": too many distance pairs for one call");
-        return LDPC_ERR_UNSUPPORTED;
-    }
-
-    // distances, close reads, candidates
-    dev_ptr<int32_t> dpa, dpb, ddist, dcand, dwidth;
-    dev_ptr<uint8_t> dclose, darows;
-    if ((rc = dev_alloc(dclose, (size_t)std::max<int64_t>(n_valid, 16)))) return rc;
-    LDPC_HIP(hipMemset(dclose.get(), 0, (size_t)std::max<int64_t>(n_valid, 16)));
-    if (P > 0) {
-        if ((rc = dev_alloc(dpa, (size_t)P))) return rc;
-        if ((rc = dev_alloc(dpb, (size_t)P))) return rc;
-        if ((rc = dev_alloc(ddist, (size_t)P))) return rc;
-        hipLaunchKernelGGL(k_plan_pairs, dim3(plan_blocks(P, 256)), b256, 0, 0, dpstart.get(),
-                           dstart.get(), S, n_valid, P, dpa.get(), dpb.get(), d_ctl);
-        LDPC_HIP(hipGetLastError());
-        if ((rc = launch_edit_distance(d_seq, dsoff.get(), dslen.get(), dpa.get(),
-                                       dpb.get(), P, std::max(ctl.max_ragged_len, 0), ddist.get())))
-            return rc;
-        hipLaunchKernelGGL(k_plan_close, dim3(plan_blocks(P, 256)), b256, 0, 0, dpa.get(), dpb.get(),
-                           ddist.get(), P, n_valid, dclose.get(), d_ctl);
-        LDPC_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_plan_cand_count, per_strand, b256, 0, 0, dstart.get(), S, n_valid, dnp.get(),
-                       dclose.get(), dncand.get(), drc.get());
-    LDPC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_plan_scan<int64_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, dncand.get(), (int64_t)S,
-                       dcptr.get());
-    LDPC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_plan_scan<int64_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, drc.get(), (int64_t)S,
-                       pd->row_ptr.get());
-    LDPC_HIP(hipGetLastError());
-    int64_t C = 0, R = 0;
-    LDPC_HIP(hipMemcpy(&C, dcptr.get() + S, sizeof C, hipMemcpyDeviceToHost));
-    LDPC_HIP(hipMemcpy(&R, pd->row_ptr.get() + S, sizeof R, hipMemcpyDeviceToHost));
-    if (C < 0 || C > n_valid || R < 0 || R > n_valid) {
-        set_error(who + ": the device plan is inconsistent");
-        return LDPC_ERR_DEVICE;
-    }
-
-    // the aligner: group s = the candidates of strand s (empty for most strands)
-    int64_t n_aligned = 0;
-    std::vector<int32_t> width((size_t)S, 0);
-    if ((rc = dev_alloc(dcand, (size_t)C))) return rc;
-    if (C > 0) {
-        if (!a.align) {
-            set_error(who + ": ragged strands need an aligner (align = 0)");
-            return LDPC_ERR_ARG;
-        }
-        hipLaunchKernelGGL(k_plan_cand_fill, per_strand, b256, 0, 0, dstart.get(), S, n_valid,
-                           dcptr.get(), C, dclose.get(), dids.get(), dcand.get(), d_ctl);
-        LDPC_HIP(hipGetLastError());
-        std::vector<int64_t> cptr((size_t)S + 1), coff((size_t)C), out_ptr((size_t)S + 1);
-        std::vector<int32_t> cand((size_t)C), clen((size_t)C), centre((size_t)S);
-        std::vector<uint8_t> out;
-        LDPC_HIP(hipMemcpy(cptr.data(), dcptr.get(), sizeof(int64_t) * (SS + 1), hipMemcpyDeviceToHost));
-        LDPC_HIP(hipMemcpy(cand.data(), dcand.get(), sizeof(int32_t) * (size_t)C, hipMemcpyDeviceToHost));
-        const int64_t skip = a.index_vals ? 0 : rs::kPrefixNt;
-        if (cptr[0] != 0 || cptr[(size_t)S] != C) {
-            set_error(who + ": the device plan is inconsistent");
-            return LDPC_ERR_DEVICE;
-        }
-        std::vector<uint8_t> cseq;     // device source: the candidates' payloads, packed
-        dev_ptr<uint8_t> dcseq;
-        const uint8_t* star_seqs = a.seqs;
-        const uint8_t* d_star_seqs = d_seq;
-        if (!src) {
-            for (int64_t c = 0; c < C; c++) {
-                const int32_t r = cand[(size_t)c];
-                if (r < 0 || r >= n || a.lengths[r] < skip) {
-                    set_error(who + ": the device plan is inconsistent");
-                    return LDPC_ERR_DEVICE;
-                }
-                coff[(size_t)c] = a.offsets[r] + skip;
-                clen[(size_t)c] = (int32_t)(a.lengths[r] - skip);
-            }
-        } else {
-            dev_ptr<int32_t> dclen;
-            dev_ptr<int64_t> dcoff;
-            int64_t T = 0;
-            if ((rc = dev_alloc(dclen, (size_t)C)) || (rc = dev_alloc(dcoff, (size_t)C + 1))) return rc;
-            hipLaunchKernelGGL(k_plan_cand_len, dim3(plan_blocks(C, 256)), b256, 0, 0, dcand.get(), C, n, d_len,
-                               (int32_t)skip, dclen.get(), d_ctl);
-            LDPC_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_plan_scan<int32_t>, dim3(1), dim3(kPlanScanThreads), 0, 0, dclen.get(), C,
-                               dcoff.get());
-            LDPC_HIP(hipGetLastError());
-            LDPC_HIP(hipMemcpy(&T, dcoff.get() + C, sizeof T, hipMemcpyDeviceToHost));
-            if (T < 0 || T > C * (int64_t)kPlanMaxLen) {
-                set_error(who + ": the device plan is inconsistent");
-                return LDPC_ERR_DEVICE;
-            }
-            if ((rc = dev_alloc(dcseq, (size_t)T))) return rc;
-            hipLaunchKernelGGL(k_plan_cand_gather, dim3(plan_blocks(C, 4)), b256, 0, 0, dcand.get(), C, n, d_seq,
-                               d_off, src->seq_bytes, (int32_t)skip, dcoff.get(), dclen.get(), T, dcseq.get(), d_ctl);
-            LDPC_HIP(hipGetLastError());
-            cseq.resize((size_t)T);
-            LDPC_HIP(hipMemcpy(coff.data(), dcoff.get(), sizeof(int64_t) * (size_t)C, hipMemcpyDeviceToHost));
-            LDPC_HIP(hipMemcpy(clen.data(), dclen.get(), sizeof(int32_t) * (size_t)C, hipMemcpyDeviceToHost));
-            if (T > 0) LDPC_HIP(hipMemcpy(cseq.data(), dcseq.get(), (size_t)T, hipMemcpyDeviceToHost));
-            LDPC_HIP(hipMemcpy(&ctl, dctl.get(), sizeof ctl, hipMemcpyDeviceToHost));
-            if (ctl.bad) {
-                set_error(who + ": the device plan is inconsistent");
-                return LDPC_ERR_DEVICE;
-            }
-            star_seqs = cseq.data();
-            d_star_seqs = dcseq.get();
-        }
-        StarCall sc{star_seqs, coff.data(), clen.data(), C, cptr.data(), (int64_t)S, centre.data(), width.data(),
-                    out_ptr.data(), nullptr, 0, nullptr, nullptr};
-        sc.out_vec = &out;
-        if ((rc = star_align_device(sc, device, workspace_bytes, nullptr, who, d_star_seqs))) return rc;
-        // the rows to upload: the aligned row (width == payload_nt), else its last byte in byte 0
-        std::vector<uint8_t> arows((size_t)C * (size_t)nt, star::kGap);
-        for (int32_t s = 0; s < S; s++) {
-            const int64_t c0 = cptr[(size_t)s], nc = cptr[(size_t)s + 1] - c0, w = width[(size_t)s];
-            if (nc == 0) continue;
-            n_aligned++;
-            for (int64_t q = 0; q < nc; q++) {
-                const uint8_t* row = out.data() + out_ptr[(size_t)s] + q * w;
-                uint8_t* dst = arows.data() + (size_t)(c0 + q) * (size_t)nt;
-                if (w == nt) std::copy(row, row + nt, dst);
-                else if (w > 0) dst[0] = row[w - 1];
-            }
-        }
-        if ((rc = upload(darows, arows.data(), arows.size()))) return rc;
-    }
-    if ((rc = upload(dwidth, width.data(), SS))) return rc;
-
-    if ((rc = dev_alloc(pd->rows, (size_t)R * (size_t)nt))) return rc;
-    if ((rc = dev_alloc(pd->row_q, (size_t)R))) return rc;
-    if (R > 0) {
-        hipLaunchKernelGGL(k_plan_rows, dim3((unsigned)std::min<int64_t>((R + 3) / 4, 2048)), b256, 0, 0,
-                           pd->row_ptr.get(), S, R, dstart.get(), n_valid, n, dcptr.get(), C,
-                           dcand.get(), darows.get(), dwidth.get(), d_seq,
-                           dsoff.get(), dslen.get(), dids.get(), d_q, nt,
-                           pd->kind.get(), pd->rows.get(), pd->row_q.get(), d_ctl);
-        LDPC_HIP(hipGetLastError());
-    }
-    LDPC_HIP(hipMemcpy(&ctl, dctl.get(), sizeof ctl, hipMemcpyDeviceToHost));
-    if (ctl.bad) {
-        set_error(who + ": the device plan is inconsistent");
-        return LDPC_ERR_DEVICE;
-    }
-    pd->R = R;
-    if (a.kind) LDPC_HIP(hipMemcpy(a.kind, pd->kind.get(), sizeof(int32_t) * SS, hipMemcpyDeviceToHost));
-    if (host_outputs) {
-        LDPC_HIP(hipMemcpy(a.row_ptr, pd->row_ptr.get(), sizeof(int64_t) * (SS + 1), hipMemcpyDeviceToHost));
-        if (R > 0) {
-            LDPC_HIP(hipMemcpy(a.rows, pd->rows.get(), (size_t)R * (size_t)nt, hipMemcpyDeviceToHost));
-            LDPC_HIP(hipMemcpy(a.row_q, pd->row_q.get(), sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost));
-        }
-    }
-    if (a.stats) {
-        a.stats[plan::kStatValid] = n_valid;
-        a.stats[plan::kStatPairs] = P;
-        a.stats[plan::kStatAligned] = n_aligned;
-        a.stats[plan::kStatAlignPairs] = C - n_aligned;
-        a.stats[plan::kStatRows] = R;
-        for (int k = 0; k < 4; k++) a.stats[plan::kStatCnumerr + k] = (int64_t)ctl.hist[k];
-    }
-    return LDPC_OK;
+    if ((rc = select_device(who.c_str(), device))) return rc;
+    PlanWork w{who, a, src, pd, device, workspace_bytes, a.n_reads, a.n_strands, a.payload_nt,
+               dim3(plan_blocks(a.n_reads, 256)), dim3(plan_blocks(a.n_strands, 256))};
+    w.h_width.assign((size_t)w.S, 0);
+    if ((rc = plan_source(w, total)) || (rc = plan_segments(w)) || (rc = plan_classify(w)) ||
+        (rc = plan_close_reads(w)) || (rc = plan_candidates(w)) || (w.C > 0 && (rc = plan_align(w))) ||
+        (rc = plan_rows(w)))
+        return rc;
+    return plan_outputs(w, host_outputs);
 }
 
 }  // namespace

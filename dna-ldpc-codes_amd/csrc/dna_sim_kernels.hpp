@@ -1,5 +1,6 @@
 // dna_sim_kernels.hpp -- the sequencing channel on the GPU (DESIGN.md sec.
-// 8.9): k_sim_reads and the ldpc_dna_sim_* entry points.  Included by dna.hip.
+// 8.9): k_sim_reads and the ldpc_dna_sim_* entry points.  Included by dna.hip,
+// whose launch() / download() helpers (hip_own.hpp) the host code uses.
 // The definition and the draws are dna_sim.hpp's (sim::reads_host is the
 // comparator, the bytes are the same).
 #pragma once
@@ -66,12 +67,9 @@ int launch_sim_reads(const uint8_t* d_strands, int32_t S, int32_t L, uint64_t se
                      int32_t nq, uint8_t* d_reads, int64_t* d_offsets, int32_t* d_lengths, int32_t* d_quals,
                      int32_t* d_strand_of, int32_t* d_bad)
 {
-    hipLaunchKernelGGL(k_sim_reads, dim3((unsigned)((n + kSimWaves - 1) / kSimWaves)), dim3(64 * kSimWaves), 0, 0,
-                       d_strands, S, L, sim::splitmix64(seed), r0, n, (uint64_t)t_sub, (uint64_t)t_ins,
-                       (uint64_t)t_del, d_q_val, d_q_lo, nq, sim::stride(L), d_reads, d_offsets, d_lengths, d_quals,
-                       d_strand_of, d_bad);
-    LDPC_HIP(hipGetLastError());
-    return LDPC_OK;
+    return launch(k_sim_reads, dim3((unsigned)((n + kSimWaves - 1) / kSimWaves)), dim3(64 * kSimWaves), 0, nullptr,
+                  d_strands, S, L, sim::splitmix64(seed), r0, n, (uint64_t)t_sub, (uint64_t)t_ins, (uint64_t)t_del,
+                  d_q_val, d_q_lo, nq, sim::stride(L), d_reads, d_offsets, d_lengths, d_quals, d_strand_of, d_bad);
 }
 
 int sim_reads_device(const sim::Args& a, int32_t device)
@@ -104,16 +102,15 @@ int sim_reads_device(const sim::Args& a, int32_t device)
                                dql.get(), a.nq, dreads.get(), nullptr, dlen.get(), dq.get(), dso.get(), dbad.get())))
         return rc;
     int32_t bad = 0;
-    LDPC_HIP(hipMemcpy(&bad, dbad.get(), sizeof bad, hipMemcpyDeviceToHost));
+    if ((rc = download(&bad, dbad.get(), 1))) return rc;
     if (bad) {
         set_error(who + ": a strand or quality index failed its range check");
         return LDPC_ERR_DEVICE;
     }
-    LDPC_HIP(hipMemcpy(a.reads, dreads.get(), bytes, hipMemcpyDeviceToHost));
-    LDPC_HIP(hipMemcpy(a.lengths, dlen.get(), sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    LDPC_HIP(hipMemcpy(a.quals, dq.get(), sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    if (a.strand_of) LDPC_HIP(hipMemcpy(a.strand_of, dso.get(), sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    return LDPC_OK;
+    if ((rc = download(a.reads, dreads.get(), bytes)) || (rc = download(a.lengths, dlen.get(), n)) ||
+        (rc = download(a.quals, dq.get(), n)))
+        return rc;
+    return a.strand_of ? download(a.strand_of, dso.get(), n) : LDPC_OK;
 }
 
 }  // namespace

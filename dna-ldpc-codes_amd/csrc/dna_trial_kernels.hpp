@@ -1,7 +1,8 @@
 // dna_trial_kernels.hpp -- the trial handle: the kernels
 // and the device backend of dna_trial.hpp's control flow, and the ldpc_trial_*
 // entry points.  Included at the end of dna.hip, which has the planner
-// (plan_device) and the count rule (dna_bit_rule) it reuses.
+// (plan_device), the count rule (dna_bit_rule) and the entry points' guard
+// (dna_guard) it reuses; kernels are started with launch() (hip_own.hpp).
 //
 // Everything of a run is enqueued on the engine's stream, the planner excepted:
 // its kernels run on the null stream, and the engine's stream waits for an
@@ -329,10 +330,10 @@ struct TrialDev {
     {
         LDPC_HIP(hipMemcpyAsync(t.rows.get(), rows, sizeof(int32_t) * (size_t)F, hipMemcpyHostToDevice, s));
         LDPC_HIP(hipMemsetAsync(t.kmax.get(), 0, sizeof(int32_t), s));
-        hipLaunchKernelGGL(k_trial_absmax, copy_grid(F), dim3(kCopyThreads), 0, s,
-                           reinterpret_cast<const uint8_t*>(t.codes.get()), t.rows.get(), t.B, t.N, (int32_t)vec16(),
-                           t.kmax.get(), t.ctl.get());
-        LDPC_HIP(hipGetLastError());
+        if (int rc = launch(k_trial_absmax, copy_grid(F), dim3(kCopyThreads), 0, s,
+                            reinterpret_cast<const uint8_t*>(t.codes.get()), t.rows.get(), t.B, t.N, (int32_t)vec16(),
+                            t.kmax.get(), t.ctl.get()))
+            return rc;
         LDPC_HIP(hipMemcpyAsync(K, t.kmax.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
         return check_flag("k_trial_absmax");
     }
@@ -346,10 +347,10 @@ struct TrialDev {
         t.batch = true;
         t.F = (int32_t)B;
         LDPC_HIP(hipMemcpyAsync(t.rows.get(), rows, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_trial_gather_spec, copy_grid(F), dim3(kCopyThreads), 0, s,
-                           reinterpret_cast<const uint8_t*>(t.codes.get()), t.rows.get(), (int32_t)F, (int32_t)k, K,
-                           t.B, t.N, (int32_t)vec16(), reinterpret_cast<uint8_t*>(t.bcodes.get()), t.ctl.get());
-        LDPC_HIP(hipGetLastError());
+        if (int rc = launch(k_trial_gather_spec, copy_grid(F), dim3(kCopyThreads), 0, s,
+                            reinterpret_cast<const uint8_t*>(t.codes.get()), t.rows.get(), (int32_t)F, (int32_t)k, K, t.B,
+                            t.N, (int32_t)vec16(), reinterpret_cast<uint8_t*>(t.bcodes.get()), t.ctl.get()))
+            return rc;
         return t.eng.decode_codes(t.bcodes.get(), table, LDPC_IN_LLR, B, max_iter, t.bhard.get(), nullptr,
                                   LDPC_POST_LLR, t.biters.get(), t.bvalid.get());
     }
@@ -362,12 +363,10 @@ struct TrialDev {
         t.F = (int32_t)B;
         // (rows stays as it is until the stats call that follows has waited for the stream)
         LDPC_HIP(hipMemcpyAsync(t.rows.get(), rows, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, s));
-        const dim3 grid((unsigned)(((int64_t)t.N + kCopyThreads * kCopyBytes - 1) / (kCopyThreads * kCopyBytes)),
-                        (unsigned)B);
-        hipLaunchKernelGGL(k_trial_gather, grid, dim3(kCopyThreads), 0, s,
-                           reinterpret_cast<const uint8_t*>(t.codes.get()), t.rows.get(), t.B, t.N, (int32_t)vec16(),
-                           reinterpret_cast<uint8_t*>(t.bcodes.get()), t.ctl.get());
-        LDPC_HIP(hipGetLastError());
+        if (int rc = launch(k_trial_gather, copy_grid(B), dim3(kCopyThreads), 0, s,
+                            reinterpret_cast<const uint8_t*>(t.codes.get()), t.rows.get(), t.B, t.N, (int32_t)vec16(),
+                            reinterpret_cast<uint8_t*>(t.bcodes.get()), t.ctl.get()))
+            return rc;
         return t.eng.decode_codes(t.bcodes.get(), table, LDPC_IN_LLR, B, max_iter, t.bhard.get(), nullptr,
                                   LDPC_POST_LLR, t.biters.get(), t.bvalid.get());
     }
@@ -377,11 +376,10 @@ struct TrialDev {
         if (re_decode) LDPC_HIP(hipMemsetAsync(t.re_decode.get(), 0, sizeof(int32_t) * (size_t)t.N, s));
         const dim3 grid((unsigned)(((int64_t)t.N + kStatThreads * kStatCols - 1) / (kStatThreads * kStatCols)),
                         (unsigned)((B + kStatRows - 1) / kStatRows));
-        hipLaunchKernelGGL(k_trial_stats, grid, dim3(kStatThreads), 0, s, t.batch ? t.bhard.get() : t.hard.get(),
-                           t.codes.get(), t.genie ? t.truth.get() : nullptr, rows ? t.rows.get() : nullptr,
-                           (int32_t)B, t.B, t.N, t.errors.get(), re_decode ? t.re_decode.get() : nullptr,
-                           t.ctl.get());
-        LDPC_HIP(hipGetLastError());
+        if (int rc = launch(k_trial_stats, grid, dim3(kStatThreads), 0, s, t.batch ? t.bhard.get() : t.hard.get(),
+                            t.codes.get(), t.genie ? t.truth.get() : nullptr, rows ? t.rows.get() : nullptr, (int32_t)B,
+                            t.B, t.N, t.errors.get(), re_decode ? t.re_decode.get() : nullptr, t.ctl.get()))
+            return rc;
         LDPC_HIP(hipMemcpyAsync(errors, t.errors.get(), sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, s));
         LDPC_HIP(hipMemcpyAsync(valid, (t.batch ? t.bvalid : t.valid).get(), (size_t)B, hipMemcpyDeviceToHost, s));
         if (re_decode)
@@ -393,11 +391,9 @@ struct TrialDev {
     {
         (void)rows;  // on the device since this decode's gather
         LDPC_HIP(hipMemcpyAsync(t.pos.get(), pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-        const dim3 grid((unsigned)(((int64_t)t.N + kCopyThreads * kCopyBytes - 1) / (kCopyThreads * kCopyBytes)),
-                        (unsigned)n);
-        hipLaunchKernelGGL(k_trial_scatter, grid, dim3(kCopyThreads), 0, s, t.bhard.get(), t.rows.get(), t.pos.get(),
-                           t.F, t.B, t.N, (int32_t)vec16(), t.hard.get(), t.ctl.get());
-        LDPC_HIP(hipGetLastError());
+        if (int rc = launch(k_trial_scatter, copy_grid(n), dim3(kCopyThreads), 0, s, t.bhard.get(), t.rows.get(),
+                            t.pos.get(), t.F, t.B, t.N, (int32_t)vec16(), t.hard.get(), t.ctl.get()))
+            return rc;
         return check_flag("k_trial_scatter");
     }
 };
@@ -539,9 +535,9 @@ int trial_plan_run(ldpc_trial* t, const std::string& who, const plan::Args& a, c
     LDPC_HIP(hipStreamWaitEvent(s, t->planned.get(), 0));
     LDPC_HIP(hipMemsetAsync(t->ctl.get(), 0, 2 * sizeof(int32_t), s));
     const dim3 grid((unsigned)((a.n_strands + 255) / 256), (unsigned)a.payload_nt);
-    hipLaunchKernelGGL(k_dna_codes, grid, dim3(256), 0, s, pd.kind.get(), pd.row_ptr.get(), pd.rows.get(),
-                       pd.row_q.get(), a.n_strands, a.payload_nt, t->codes.get(), t->ctl.get() + 1);
-    LDPC_HIP(hipGetLastError());
+    if (int rc = launch(k_dna_codes, grid, dim3(256), 0, s, pd.kind.get(), pd.row_ptr.get(), pd.rows.get(),
+                        pd.row_q.get(), a.n_strands, a.payload_nt, t->codes.get(), t->ctl.get() + 1))
+        return rc;
     int32_t ov = 0;
     LDPC_HIP(hipMemcpyAsync(&ov, t->ctl.get() + 1, sizeof ov, hipMemcpyDeviceToHost, s));
     LDPC_HIP(hipStreamSynchronize(s));  // the plan is released below; ov is read
@@ -641,17 +637,6 @@ int trial_run_sim(ldpc_trial* t, const SimCall& c, const int32_t* strand_index_v
     return trial_plan_run(t, who, a, &src, t0, workspace_bytes, eps, max_iter, faithful, out);
 }
 
-template <class F>
-int trial_guard(const char* who, F&& f)
-{
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        set_error(std::string(who) + ": out of host memory");
-        return LDPC_ERR_DEVICE;
-    }
-}
-
 }  // namespace
 }  // namespace ldpc
 
@@ -661,7 +646,7 @@ int ldpc_dna_trial_host(const int8_t* codes, int32_t n_cw, int32_t N, const uint
                         ldpc_trial_decode_fn decode, void* user, double eps, int32_t max_iter, int32_t faithful,
                         ldpc_trial_result* out)
 {
-    return ldpc::trial_guard("ldpc_dna_trial_host", [&] {
+    return ldpc::dna_guard("ldpc_dna_trial_host", [&] {
         std::string err;
         const int rc = ldpc::trial::run_host(codes, n_cw, N, codewords, decode, user, eps, max_iter, faithful, out, &err);
         if (rc) set_error("ldpc_dna_trial_host: " + err);
@@ -673,7 +658,7 @@ int ldpc_dna_trial_host_spec(const int8_t* codes, int32_t n_cw, int32_t N, const
                              ldpc_trial_decode_fn decode, void* user, double eps, int32_t max_iter, int32_t faithful,
                              ldpc_trial_result* out, int32_t steps, ldpc_trial_counters* counters)
 {
-    return ldpc::trial_guard("ldpc_dna_trial_host_spec", [&] {
+    return ldpc::dna_guard("ldpc_dna_trial_host_spec", [&] {
         std::string err;
         const int rc = ldpc::trial::run_host_spec(codes, n_cw, N, codewords, decode, user, eps, max_iter, faithful,
                                                   steps, counters, out, &err);
@@ -686,7 +671,7 @@ ldpc_trial* ldpc_trial_create(const ldpc_graph* g, int32_t device, int32_t algo,
                               const uint8_t* codewords, const ldpc_schedule* schedule, int* err)
 {
     std::unique_ptr<ldpc_trial> t;
-    const int rc = ldpc::trial_guard("ldpc_trial_create",
+    const int rc = ldpc::dna_guard("ldpc_trial_create",
                                      [&] { return ldpc::trial_create(g, device, algo, n_cw, codewords, schedule, t); });
     if (err) *err = rc;
     return rc ? nullptr : t.release();
@@ -699,7 +684,7 @@ int ldpc_trial_run_reads(ldpc_trial* t, const uint8_t* seqs, const int64_t* offs
                          int32_t n_strands, int32_t payload_nt, int32_t align, int64_t workspace_bytes, double eps,
                          int32_t max_iter, int32_t faithful, ldpc_trial_result* out)
 {
-    return ldpc::trial_guard("ldpc_trial_run_reads", [&] {
+    return ldpc::dna_guard("ldpc_trial_run_reads", [&] {
         return ldpc::trial_run_reads(t, plan_args(seqs, offsets, lengths, quals, n_reads, index_vals, strands, n_strands,
                                                   payload_nt, align, out ? out->kind : nullptr, nullptr, nullptr,
                                                   nullptr, out ? out->stats : nullptr),
@@ -709,7 +694,7 @@ int ldpc_trial_run_reads(ldpc_trial* t, const uint8_t* seqs, const int64_t* offs
 
 int ldpc_trial_set_strands(ldpc_trial* t, const uint8_t* strands, int64_t n_strands, int32_t strand_nt)
 {
-    return ldpc::trial_guard("ldpc_trial_set_strands",
+    return ldpc::dna_guard("ldpc_trial_set_strands",
                              [&] { return ldpc::trial_set_strands(t, strands, n_strands, strand_nt); });
 }
 
@@ -718,7 +703,7 @@ int ldpc_trial_run_sim(ldpc_trial* t, uint64_t seed, int64_t r0, int64_t n_reads
                        const int32_t* strand_index_vals, int32_t align, int64_t workspace_bytes, double eps,
                        int32_t max_iter, int32_t faithful, ldpc_trial_result* out)
 {
-    return ldpc::trial_guard("ldpc_trial_run_sim", [&] {
+    return ldpc::dna_guard("ldpc_trial_run_sim", [&] {
         return ldpc::trial_run_sim(t, ldpc::SimCall{seed, r0, n_reads, t_sub, t_ins, t_del, q_val, q_lo, nq},
                                    strand_index_vals, align, workspace_bytes, eps, max_iter, faithful, out);
     });
@@ -727,13 +712,13 @@ int ldpc_trial_run_sim(ldpc_trial* t, uint64_t seed, int64_t r0, int64_t n_reads
 int ldpc_trial_run_codes(ldpc_trial* t, const int8_t* codes, int64_t B, double eps, int32_t max_iter,
                          int32_t faithful, ldpc_trial_result* out)
 {
-    return ldpc::trial_guard("ldpc_trial_run_codes",
+    return ldpc::dna_guard("ldpc_trial_run_codes",
                              [&] { return ldpc::trial_run_codes(t, codes, B, eps, max_iter, faithful, out); });
 }
 
 int ldpc_trial_set_speculation(ldpc_trial* t, int32_t steps)
 {
-    return ldpc::trial_guard("ldpc_trial_set_speculation", [&] { return ldpc::trial_set_speculation(t, steps); });
+    return ldpc::dna_guard("ldpc_trial_set_speculation", [&] { return ldpc::trial_set_speculation(t, steps); });
 }
 
 int ldpc_trial_get_counters(const ldpc_trial* t, ldpc_trial_counters* out)

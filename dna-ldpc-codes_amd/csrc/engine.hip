@@ -1070,25 +1070,21 @@ int encode_launch(const EncoderDev& d, hipStream_t stream, const uint8_t* d_msg,
         const unsigned tiles = (unsigned)((Bc + TILE - 1) / TILE);
         const uint8_t* m = d_msg + (size_t)b0 * K;
         const int vec4 = ((reinterpret_cast<uintptr_t>(m) | K) & 3) == 0;
-        LDPC_HIP(hipMemsetAsync(w, 0, (size_t)tiles * N * sizeof(uint64_t), stream));
-        hipLaunchKernelGGL(k_enc_pack, dim3((unsigned)((K + ENC_PACK_COLS - 1) / ENC_PACK_COLS), tiles), dim3(256), 0, stream,
-                           m, d.info_pos, w, Bc, d.K, d.N, vec4);
-        if (d.M > 0)
-            hipLaunchKernelGGL(k_enc_rows, dim3((unsigned)((d.M + 3) / 4), tiles), dim3(256), 0, stream, w, d.row_ptr,
-                               d.col_idx, s, d.M, d.N);
-        if (d.rank > 0) {
-            const dim3 grid((unsigned)((d.rank + ENC_DENSE_ROWS - 1) / ENC_DENSE_ROWS), tiles);
-            if (in_lds)
-                hipLaunchKernelGGL(k_enc_dense<true>, grid, dim3(256), (uint32_t)s_bytes, stream, d.T, s, d.par_pos, w,
-                                   d.rank, d.M, d.Mw, d.N);
-            else
-                hipLaunchKernelGGL(k_enc_dense<false>, grid, dim3(256), 0, stream, d.T, s, d.par_pos, w, d.rank, d.M,
-                                   d.Mw, d.N);
-        }
+        const dim3 b256(256), dense((unsigned)((d.rank + ENC_DENSE_ROWS - 1) / ENC_DENSE_ROWS), tiles);
         const int64_t nblk = Bc * (((int64_t)N + 255) / 256);
-        hipLaunchKernelGGL(k_unpack_hard, dim3((unsigned)std::min<int64_t>(nblk, 1 << 20)), dim3(256), 0, stream, w,
-                           d_cw + (size_t)b0 * N, Bc, d.N);
-        LDPC_HIP(hipGetLastError());
+        int rc;
+        LDPC_HIP(hipMemsetAsync(w, 0, (size_t)tiles * N * sizeof(uint64_t), stream));
+        if ((rc = launch(k_enc_pack, dim3((unsigned)((K + ENC_PACK_COLS - 1) / ENC_PACK_COLS), tiles), b256, 0, stream, m,
+                         d.info_pos, w, Bc, d.K, d.N, vec4)) ||
+            (d.M > 0 && (rc = launch(k_enc_rows, dim3((unsigned)((d.M + 3) / 4), tiles), b256, 0, stream, w, d.row_ptr,
+                                     d.col_idx, s, d.M, d.N))) ||
+            (d.rank > 0 && (rc = in_lds ? launch(k_enc_dense<true>, dense, b256, (uint32_t)s_bytes, stream, d.T, s,
+                                                 d.par_pos, w, d.rank, d.M, d.Mw, d.N)
+                                        : launch(k_enc_dense<false>, dense, b256, 0, stream, d.T, s, d.par_pos, w, d.rank,
+                                                 d.M, d.Mw, d.N))) ||
+            (rc = launch(k_unpack_hard, dim3((unsigned)std::min<int64_t>(nblk, 1 << 20)), b256, 0, stream, w,
+                         d_cw + (size_t)b0 * N, Bc, d.N)))
+            return rc;
     }
     return LDPC_OK;
 }

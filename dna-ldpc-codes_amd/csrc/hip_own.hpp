@@ -1,7 +1,8 @@
 // hip_own.hpp -- owning handles for the HIP objects of the host code: device
 // and pinned host memory, events, streams.  Each is a std::unique_ptr with a
-// deleter; the helpers return LDPC_* codes and set the thread-local error as
-// LDPC_HIP does.  No device code.
+// deleter; the helpers (allocation, the blocking copies up and down, a kernel
+// launch) return LDPC_* codes and set the thread-local error as LDPC_HIP does.
+// No device code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -76,6 +77,25 @@ int upload(dev_ptr<T>& out, const std::vector<T>& v)
 {
     return upload(out, v.data(), v.size());
 }
+
+// src[0, n) of device memory into dst (blocking)
+template <typename T>
+int download(T* dst, const T* src, size_t n)
+{
+    if (n) LDPC_HIP(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
+    return LDPC_OK;
+}
+
+#if defined(__HIPCC__)
+// kernel<<<grid, block, lds_bytes, stream>>>(args...) and the launch's error
+template <typename F, typename... A>
+int launch(F kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const A&... args)
+{
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+    LDPC_HIP(hipGetLastError());
+    return LDPC_OK;
+}
+#endif
 
 inline int make_event(Event& out, unsigned flags = hipEventDisableTiming)
 {

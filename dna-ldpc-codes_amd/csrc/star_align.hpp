@@ -1,7 +1,9 @@
 // star_align.hpp -- the centre-star multiple alignment of one group of reads
 // (the place MUSCLE has in the reference,
 // ex_decoder/decoder.py:201-207).  Header-only, no HIP needed: the host path
-// of ldpc_dna_star_align[_host] and the comparator of the kernels in dna.hip.
+// of ldpc_dna_star_align[_host], the comparator of the kernels in dna.hip, and
+// (at the end) the device path's planning: which groups the kernel takes,
+// their pairs packed into blocks and passes, the check of a returned script.
 //
 // Definition.  A group is k >= 1 reads (any bytes, any length), in candidate
 // order.
@@ -212,6 +214,129 @@ inline int64_t group_scripts(const uint8_t* const* reads, const int64_t* lens, i
     for (int64_t a = 0; a < k; a++)
         if (a != centre) pair_script(reads[a], lens[a], reads[centre], lens[centre], &scripts[a]);
     return centre;
+}
+
+// --- the device path's planning (ldpc_dna_star_align, dna.hip): which groups
+// k_star_align_pairs takes and how their (read, centre) pairs are laid out in
+// blocks of lanes and passes over the workspace.  Plain arrays in and out.
+
+constexpr int32_t kDevMaxLen = 800;  // the DP row and the centre of 64 lanes in LDS
+
+// Workspace words of one lane-interleaved block: rows x words per row x 64 lanes.
+inline int64_t block_words(int64_t m, int64_t wpr) { return m * wpr * 64; }
+// Words of one table row against a centre of n bytes: 2 bits per cell.
+inline int64_t words_per_row(int64_t n) { return (n + 15) / 16; }
+
+// A group the device can take: two reads or more, none longer than kDevMaxLen.
+inline bool device_eligible(const int32_t* len, int64_t k)
+{
+    bool ok = k >= 2;
+    for (int64_t q = 0; q < k && ok; q++) ok = len[q] <= kDevMaxLen;
+    return ok;
+}
+
+// The budget rule: a group with a pair whose own block (64 lanes x m rows x
+// ceil(n / 16) words) is beyond the budget goes to the host.
+inline bool within_budget(const int32_t* len, int64_t k, int64_t centre, int64_t budget_words)
+{
+    const int64_t wpr = words_per_row(len[centre]);
+    for (int64_t q = 0; q < k; q++)
+        if (q != centre && block_words(len[q], wpr) > budget_words) return false;
+    return true;
+}
+
+// Pair p is read pr[p] against centre pc[p] (sequence numbers); its script goes
+// to at_off[p] (n bytes; cnt at at_off[p] + p) and ins_off[p] (m bytes).  Block b
+// is pairs blk_first[b] .. blk_first[b + 1], blk_wpr[b] words per table row,
+// blk_words[b] workspace words.
+struct PairBlocks {
+    std::vector<int32_t> pr, pc, blk_wpr;
+    std::vector<int64_t> at_off, ins_off, blk_first, blk_words;
+    int64_t at_total = 0, ins_total = 0;
+    int64_t n_host = 0;  // groups of two reads or more left to the host
+    int32_t max_n = 0;   // longest centre
+};
+
+// The pairs of the groups with on_dev[g] set, group by group in read order, cut
+// into blocks of at most 64 pairs whose max(m) * max(ceil(n / 16)) * 64 words
+// fit the budget.  centre[g] is the centre's index inside group g.
+inline PairBlocks pack_pairs(const int32_t* lengths, const int64_t* group_ptr, int64_t n_groups, const int64_t* centre,
+                             const uint8_t* on_dev, int64_t budget_words)
+{
+    PairBlocks pb;
+    int64_t cnt = 0, bm = 0, bw = 0;
+    auto close_block = [&] {
+        pb.blk_words.push_back(block_words(bm, bw));
+        pb.blk_wpr.push_back((int32_t)bw);
+        cnt = bm = bw = 0;
+    };
+    for (int64_t g = 0; g < n_groups; g++) {
+        const int64_t g0 = group_ptr[g], k = group_ptr[g + 1] - g0;
+        if (!on_dev[g]) {
+            if (k >= 2) pb.n_host++;
+            continue;
+        }
+        const int64_t c = g0 + centre[g], n = lengths[c], wpr = words_per_row(n);
+        if ((int32_t)n > pb.max_n) pb.max_n = (int32_t)n;
+        for (int64_t q = g0; q < g0 + k; q++) {
+            if (q == c) continue;
+            const int64_t m = lengths[q], nm = m > bm ? m : bm, nw = wpr > bw ? wpr : bw;
+            if (cnt == 64 || (cnt > 0 && block_words(nm, nw) > budget_words)) close_block();
+            if (cnt == 0) pb.blk_first.push_back((int64_t)pb.pr.size());
+            cnt++;
+            if (m > bm) bm = m;
+            if (wpr > bw) bw = wpr;
+            pb.pr.push_back((int32_t)q);
+            pb.pc.push_back((int32_t)c);
+            pb.at_off.push_back(pb.at_total);
+            pb.ins_off.push_back(pb.ins_total);
+            pb.at_total += n;
+            pb.ins_total += m;
+        }
+    }
+    if (cnt > 0) close_block();
+    pb.blk_first.push_back((int64_t)pb.pr.size());
+    return pb;
+}
+
+// The passes: runs of blocks whose pieces of the workspace fit the budget
+// together.  Block b's piece starts at word blk_ws[b]; pass q is blocks
+// pass_first[q] .. pass_first[q + 1]; the workspace needs ws_words words.
+struct Passes {
+    std::vector<int64_t> blk_ws, pass_first;
+    int64_t ws_words = 0;
+};
+
+inline Passes cut_passes(const std::vector<int64_t>& blk_words, int64_t budget_words)
+{
+    Passes ps;
+    const size_t nb = blk_words.size();
+    ps.blk_ws.resize(nb);
+    int64_t acc = 0;
+    for (size_t b = 0; b < nb; b++) {
+        if (b == 0 || acc + blk_words[b] > budget_words) {
+            ps.pass_first.push_back((int64_t)b);
+            acc = 0;
+        }
+        ps.blk_ws[b] = acc;
+        acc += blk_words[b];
+        if (acc > ps.ws_words) ps.ws_words = acc;
+    }
+    ps.pass_first.push_back((int64_t)nb);
+    return ps;
+}
+
+// A script's cnt[n + 1] as the device returned it, for a read of m bytes: every
+// entry in 0..m and their sum *t <= m (then ins holds its m - *t .. m).
+inline bool script_consistent(const int32_t* cnt, int64_t m, int64_t n, int64_t* t)
+{
+    bool ok = true;
+    *t = 0;
+    for (int64_t j = 0; j <= n; j++) {
+        ok = ok && cnt[j] >= 0 && cnt[j] <= m;
+        *t += cnt[j];
+    }
+    return ok && *t <= m;
 }
 
 }  // namespace star

@@ -18,7 +18,8 @@
 //   aligned widths equal to and different from payload_nt;
 // * raw reads: prefixes made with rs_index.hpp, a read of 16 bytes (an empty
 //   payload), shorter ones and a non-ACGT prefix (dropped);
-// * the argument errors;
+// * the argument errors; the shared extent check of ragged reads
+//   (ragged_reads.hpp) and the aligned-row rule (plan::aligned_row) on their own;
 // * a dense case: 60 strands of 2..7 mutated reads, planned twice.
 // Exit status 0 iff every check held.
 #include <cstdint>
@@ -217,6 +218,41 @@ int main()
         a.row_ptr = nullptr;
         CHECK(!plan::check_args(a, &total).empty() && plan::check_args(a, &total, false).empty() == false, "null row_ptr");
         n_cases += 5;
+    }
+    {  // the extent check of ragged reads: arrays of exact size
+        int64_t total = -1;
+        int32_t max_len = -1;
+        CHECK(ragged::check(nullptr, nullptr, nullptr, 0, &total).empty() && total == 0, "extent: n = 0");
+        auto off = exact(std::vector<int64_t>{INT64_MAX, 4}), ovf = exact(std::vector<int64_t>{0, INT64_MAX - 2});
+        auto len = exact(std::vector<int32_t>{0, 0}), len3 = exact(std::vector<int32_t>{1, 3}), neg = exact(std::vector<int32_t>{2, -1});
+        CHECK(ragged::check(nullptr, off.get(), len.get(), 2, &total).empty() && total == 0,
+              "extent: empty reads at large offsets span nothing");
+        CHECK(ragged::extent(off.get(), len.get(), 2, &total, true, &max_len).empty() && total == INT64_MAX && max_len == 0,
+              "extent: empty reads counted");
+        uint8_t byte = 0;
+        CHECK(ragged::check(&byte, ovf.get(), len3.get(), 2, &total) == "negative or overflowing length/offset",
+              "extent: offset + length overflows");
+        CHECK(ragged::check(&byte, off.get() + 1, neg.get(), 1, &total).empty() && total == 6, "extent: one read");
+        CHECK(ragged::check(nullptr, off.get() + 1, neg.get(), 1, &total) == "null sequences", "extent: null sequences");
+        CHECK(ragged::check(&byte, off.get(), neg.get(), 2, &total) == "negative or overflowing length/offset",
+              "extent: negative length");
+        CHECK(ragged::extent(ovf.get(), len3.get(), 1, &total, false, &max_len).empty() && total == 1 && max_len == 1,
+              "extent: longest read");
+        n_cases += 8;
+    }
+    {  // the aligned-row rule at width == nt, 0, nt - 1 and nt + 1: source and destination of exact size
+        for (int64_t width : {(int64_t)nt, (int64_t)0, (int64_t)nt - 1, (int64_t)nt + 1}) {
+            std::vector<uint8_t> src;
+            for (int64_t j = 0; j < width; j++) src.push_back((uint8_t)('a' + j));
+            auto row = exact(src);
+            auto dst = exact(std::vector<uint8_t>((size_t)nt, (uint8_t)'-'));
+            plan::aligned_row(row.get(), width, nt, dst.get());
+            std::string want((size_t)nt, '-');
+            if (width == nt) want.assign(src.begin(), src.end());
+            else if (width > 0) want[0] = (char)src.back();
+            CHECK(std::string((const char*)dst.get(), (size_t)nt) == want, "aligned_row at width %lld", (long long)width);
+            n_cases++;
+        }
     }
     {  // dense: 60 strands of 2..7 reads, mutated copies of a 40-nt payload, shuffled; twice the same
         const int32_t dnt = 40;

@@ -12,8 +12,11 @@
 // * every single substitution, insertion and deletion of a 10-nt parent,
 //   paired with the parent in both orders: distance 1, width 10 or 11, each
 //   row without '-' is its read;
-// * a group of five reads with ties, and one of two 700-nt reads.
-// Exit status 0 iff every check held.
+// * a group of five reads with ties, and one of two 700-nt reads;
+// * the device path's planning (device_eligible, within_budget, pack_pairs,
+//   cut_passes) on the smallest shapes at which a block or a pass is cut, with
+//   the layout's invariants asserted for every case, and script_consistent.
+// Exit status 0 iff every check held; the planner's case count goes to stderr.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -90,6 +93,179 @@ static void check_rows(const std::vector<std::string>& reads, const Aligned& r, 
     }
 }
 
+// --- the device path's planning ----------------------------------------------
+struct Planned {
+    std::vector<uint8_t> on_dev;
+    PairBlocks pb;
+    Passes ps;
+};
+
+static int n_planned = 0;
+
+// groups[g] = the lengths of group g's reads, the centre is read 0 of each.  The
+// steps of ldpc_dna_star_align in their order, on arrays of exact size, and the
+// invariants of the layout.
+static Planned plan(const std::vector<std::vector<int32_t>>& groups, int64_t budget, const char* what)
+{
+    n_planned++;
+    const int64_t G = (int64_t)groups.size();
+    std::vector<int32_t> lens;
+    std::vector<int64_t> gp{0};
+    for (const auto& g : groups) {
+        lens.insert(lens.end(), g.begin(), g.end());
+        gp.push_back((int64_t)lens.size());
+    }
+    std::unique_ptr<int32_t[]> len(new int32_t[lens.size() + (lens.empty() ? 1 : 0)]);
+    std::copy(lens.begin(), lens.end(), len.get());
+    std::unique_ptr<int64_t[]> ptr(new int64_t[gp.size()]), centre(new int64_t[(size_t)G + (G ? 0 : 1)]);
+    std::copy(gp.begin(), gp.end(), ptr.get());
+    Planned r;
+    r.on_dev.assign((size_t)G, 0);
+    int64_t want_host = 0;
+    std::vector<int32_t> want_pr, want_pc;
+    for (int64_t g = 0; g < G; g++) {
+        const int64_t g0 = gp[(size_t)g], k = gp[(size_t)g + 1] - g0;
+        centre[(size_t)g] = 0;
+        r.on_dev[(size_t)g] = device_eligible(len.get() + g0, k) && within_budget(len.get() + g0, k, 0, budget);
+        if (!r.on_dev[(size_t)g]) want_host += k >= 2;
+        for (int64_t q = 1; q < k && r.on_dev[(size_t)g]; q++) {
+            want_pr.push_back((int32_t)(g0 + q));
+            want_pc.push_back((int32_t)g0);
+        }
+    }
+    std::unique_ptr<uint8_t[]> od(new uint8_t[(size_t)G + (G ? 0 : 1)]);
+    std::copy(r.on_dev.begin(), r.on_dev.end(), od.get());
+    r.pb = pack_pairs(len.get(), ptr.get(), G, centre.get(), od.get(), budget);
+    r.ps = cut_passes(r.pb.blk_words, budget);
+    const PairBlocks& pb = r.pb;
+    const Passes& ps = r.ps;
+    const size_t P = pb.pr.size(), NB = pb.blk_words.size();
+
+    // every pair of an on-device group once, in group then read order, never the centre with itself
+    CHECK(pb.pr == want_pr && pb.pc == want_pc && pb.n_host == want_host, "%s: pairs or host groups", what);
+    for (size_t p = 0; p < P && p < pb.pc.size(); p++) CHECK(pb.pr[p] != pb.pc[p], "%s: pair %zu is the centre with itself", what, p);
+    // running sums
+    CHECK(pb.at_off.size() == P && pb.ins_off.size() == P, "%s: offset counts", what);
+    int64_t at = 0, ins = 0;
+    int32_t max_n = 0;
+    for (size_t p = 0; p < P && pb.at_off.size() == P && pb.ins_off.size() == P; p++) {
+        CHECK(pb.at_off[p] == at && pb.ins_off[p] == ins, "%s: offsets of pair %zu", what, p);
+        at += len[(size_t)pb.pc[p]];
+        ins += len[(size_t)pb.pr[p]];
+        max_n = std::max(max_n, len[(size_t)pb.pc[p]]);
+    }
+    CHECK(pb.at_total == at && pb.ins_total == ins && pb.max_n == max_n, "%s: totals", what);
+    // blocks: 1..64 pairs each, in order, all pairs; words = max m x wpr x 64 within the budget
+    CHECK(pb.blk_first.size() == NB + 1 && pb.blk_wpr.size() == NB && pb.blk_first[0] == 0 &&
+              pb.blk_first.back() == (int64_t)P,
+          "%s: block list", what);
+    if (pb.blk_first.size() != NB + 1 || pb.blk_wpr.size() != NB || pb.blk_first.back() != (int64_t)P) return r;
+    for (size_t b = 0; b < NB; b++) {
+        const int64_t p0 = pb.blk_first[b], p1 = pb.blk_first[b + 1];
+        CHECK(p1 - p0 >= 1 && p1 - p0 <= 64 && p0 >= 0, "%s: block %zu holds %lld pairs", what, b, (long long)(p1 - p0));
+        if (p1 <= p0 || p0 < 0) return r;
+        int64_t mm = 0;
+        for (int64_t p = p0; p < p1; p++) {
+            mm = std::max<int64_t>(mm, len[(size_t)pb.pr[(size_t)p]]);
+            CHECK(pb.blk_wpr[b] >= (len[(size_t)pb.pc[(size_t)p]] + 15) / 16, "%s: block %zu words per row", what, b);
+        }
+        CHECK(pb.blk_words[b] == mm * pb.blk_wpr[b] * 64, "%s: block %zu has %lld words", what, b, (long long)pb.blk_words[b]);
+        CHECK(pb.blk_words[b] <= budget, "%s: block %zu is beyond the budget", what, b);
+    }
+    // passes partition the blocks in order; inside one the pieces are disjoint and end within the budget
+    CHECK(ps.blk_ws.size() == NB && !ps.pass_first.empty() && ps.pass_first[0] == 0 && ps.pass_first.back() == (int64_t)NB,
+          "%s: pass list", what);
+    if (ps.blk_ws.size() != NB || ps.pass_first.empty() || ps.pass_first.back() != (int64_t)NB) return r;
+    int64_t ws_words = 0;
+    for (size_t q = 0; q + 1 < ps.pass_first.size(); q++) {
+        const int64_t b0 = ps.pass_first[q], b1 = ps.pass_first[q + 1];
+        CHECK(b1 > b0 && b0 >= 0, "%s: pass %zu is empty", what, q);
+        if (b1 <= b0 || b0 < 0) return r;
+        for (int64_t x = b0; x < b1; x++) {
+            const int64_t x0 = ps.blk_ws[(size_t)x], x1 = x0 + pb.blk_words[(size_t)x];
+            CHECK(x0 >= 0 && x1 <= budget, "%s: block %lld ends at word %lld", what, (long long)x, (long long)x1);
+            ws_words = std::max(ws_words, x1);
+            for (int64_t y = x + 1; y < b1; y++) {
+                const int64_t y0 = ps.blk_ws[(size_t)y], y1 = y0 + pb.blk_words[(size_t)y];
+                CHECK(x1 <= y0 || y1 <= x0, "%s: blocks %lld and %lld overlap", what, (long long)x, (long long)y);
+            }
+        }
+    }
+    CHECK(ps.ws_words == ws_words, "%s: %lld workspace words", what, (long long)ps.ws_words);
+    return r;
+}
+
+static int64_t n_passes(const Planned& r) { return (int64_t)r.ps.pass_first.size() - 1; }
+
+static void check_planner()
+{
+    using V64 = std::vector<int64_t>;
+    // one group of 66 one-byte reads: 65 pairs, every block 64 words whatever its pair count
+    const std::vector<std::vector<int32_t>> g66{std::vector<int32_t>(66, 1)};
+    Planned r = plan(g66, 128, "66 reads, 128");
+    CHECK(r.pb.blk_first == (V64{0, 64, 65}) && r.pb.blk_words == (V64{64, 64}) && n_passes(r) == 1 && r.ps.ws_words == 128 &&
+              r.ps.blk_ws == (V64{0, 64}),
+          "66 reads, budget 128");
+    r = plan(g66, 64, "66 reads, 64");
+    CHECK(r.pb.blk_first == (V64{0, 64, 65}) && r.ps.pass_first == (V64{0, 1, 2}) && r.ps.blk_ws == (V64{0, 0}) &&
+              r.ps.ws_words == 64,
+          "66 reads, budget 64");
+    r = plan(g66, 63, "66 reads, 63");
+    CHECK(!r.on_dev[0] && r.pb.pr.empty() && r.pb.n_host == 1 && n_passes(r) == 0 && r.ps.ws_words == 0, "66 reads, budget 63");
+
+    // words per row 1 against 2
+    const std::vector<std::vector<int32_t>> g2{{16, 3}, {17, 3}};
+    r = plan(g2, 384, "[16,3] [17,3], 384");
+    CHECK(r.pb.blk_first == (V64{0, 2}) && r.pb.blk_words == (V64{384}) && r.pb.blk_wpr == (std::vector<int32_t>{2}),
+          "[16,3] [17,3], budget 384");
+    r = plan(g2, 383, "[16,3] [17,3], 383");
+    CHECK(r.on_dev[0] && !r.on_dev[1] && r.pb.n_host == 1 && r.pb.blk_first == (V64{0, 1}) && r.pb.blk_words == (V64{192}),
+          "[16,3] [17,3], budget 383");
+
+    // 256 and 128 words alone, 512 together
+    const std::vector<std::vector<int32_t>> g3{{16, 4}, {32, 1}};
+    r = plan(g3, 512, "[16,4] [32,1], 512");
+    CHECK(r.pb.blk_first == (V64{0, 2}) && r.pb.blk_words == (V64{512}), "[16,4] [32,1], budget 512");
+    r = plan(g3, 511, "[16,4] [32,1], 511");
+    CHECK(r.pb.blk_first == (V64{0, 1, 2}) && r.pb.blk_words == (V64{256, 128}) && n_passes(r) == 1 &&
+              r.ps.blk_ws == (V64{0, 256}) && r.ps.ws_words == 384,
+          "[16,4] [32,1], budget 511");
+    r = plan(g3, 255, "[16,4] [32,1], 255");
+    CHECK(!r.on_dev[0] && r.on_dev[1] && r.pb.n_host == 1 && r.pb.blk_words == (V64{128}) &&
+              r.pb.pr == (std::vector<int32_t>{3}) && r.pb.pc == (std::vector<int32_t>{2}),
+          "[16,4] [32,1], budget 255");
+
+    // an empty read, an empty centre, k = 0 and k = 1: 0-word blocks at any budget, no host group
+    const std::vector<std::vector<int32_t>> ge{{5, 0}, {}, {7}, {0, 5}};
+    r = plan(ge, 0, "empty reads, 0");
+    CHECK(r.on_dev[0] && !r.on_dev[1] && !r.on_dev[2] && r.on_dev[3] && r.pb.n_host == 0 && r.pb.blk_words == (V64{0, 0}) &&
+              r.pb.pr == (std::vector<int32_t>{1, 4}) && n_passes(r) == 1 && r.ps.ws_words == 0,
+          "empty reads, budget 0");
+    r = plan(ge, 320, "empty reads, 320");  // together: 5 rows x 1 word
+    CHECK(r.pb.n_host == 0 && r.pb.blk_first == (V64{0, 2}) && r.pb.blk_words == (V64{320}), "empty reads, budget 320");
+
+    // the kernel's length limit
+    r = plan({{801, 3}}, 1 << 20, "801 bytes");
+    CHECK(!r.on_dev[0] && r.pb.n_host == 1 && r.pb.pr.empty(), "a read of 801 bytes");
+    r = plan({{800, 3}, {3, 800}}, 1 << 22, "800 bytes");  // 800 rows x 50 words
+    CHECK(r.on_dev[0] && r.on_dev[1] && r.pb.n_host == 0 && r.pb.blk_words == (V64{800 * 50 * 64}) && r.pb.max_n == 800,
+          "reads of 800 bytes");
+    r = plan({}, 100, "no groups");
+    CHECK(r.pb.blk_first == (V64{0}) && n_passes(r) == 0, "no groups");
+
+    // a returned script: m = 3, n = 2
+    int64_t t = -1;
+    int32_t cnt[3] = {1, 0, 2};
+    CHECK(script_consistent(cnt, 3, 2, &t) && t == 3, "a consistent script");
+    cnt[1] = -1;
+    CHECK(!script_consistent(cnt, 3, 2, &t), "cnt[j] = -1");
+    cnt[1] = 4;
+    cnt[0] = cnt[2] = 0;
+    CHECK(!script_consistent(cnt, 3, 2, &t), "cnt[j] = m + 1");
+    cnt[0] = 2, cnt[1] = 1, cnt[2] = 1;
+    CHECK(!script_consistent(cnt, 3, 2, &t) && t == 4, "sum = m + 1");
+}
+
 int main()
 {
     // empty reads and k = 1
@@ -150,6 +326,8 @@ int main()
     r = align({a, b});
     check_rows({a, b}, r, "long reads");
     CHECK(r.dist[1] == 5 && r.width == 702, "long reads: distance %ld width %ld", (long)r.dist[1], (long)r.width);
+    check_planner();
+    std::fprintf(stderr, "star_check: %d planner cases\n", n_planned);
     if (!fails) std::printf("star_check ok: %ld single-edit pairs\n", pairs);
     return fails ? 1 : 0;
 }
